@@ -18,8 +18,14 @@ GLOBAL problem, cut into N leaf-aligned shards.  `--scaling weak`: every rank ho
 the global model is N times larger.
 `--mode`: how linear leaves are fitted (include/rmi_hip.h, rmi_hip_set_fit_mode): exact (default: the reference's
 recurrence per leaf in reference order -- bucket ids, error integers AND coefficients bit-identical; `value` is quoted in
-this mode, and `parity_check` in the same JSON line says what the oracle found) | onepass_guarded | onepass (the
+this mode, and `parity_check` in the same JSON line of a --full run says what the oracle found) | onepass_guarded | onepass (the
 sufficient-statistics modes: side figure `fast_mode`, coefficients only to the reference's own rounding noise).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: `value` and `ms_per_step` with the roofline of the
+timed steps themselves.  `--full` adds everything that takes runs of its own: the measured read bandwidth, the 200-step
+protocol, the other fit mode, two trainings in flight, the PCIe-inclusive and fast-root figures, the CPU baseline with the
+parity check against the oracle, the other BASELINE configurations, the environment and the counter files of profiles/.
+`--dump-outputs DIR` writes what the last timed step computed (per-leaf arrays and the model's aggregates) as DIR/<name>.npy.
 
 Launch (N>1): python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
               --master-port P bench.py --gpus N --steps K --warmup W
@@ -44,6 +50,7 @@ KERNELS_LANES = ["k_leaf_lanes", "k_lane_reduce", "-", "-", "-"]                
 KERNELS_LANES_INSTREAM = ["k_leaf_lanes", "k_list", "k_list_tail", "k_finalize_listed+stats", "-"]    # RMI_HIP_OPT_TAIL=0
 KERNELS_ONEPASS = ["k_sigma2", "k_fill", "k_list", "k_list_tail", "k_finalize+stats"]
 MODES = {"exact": 0, "onepass_guarded": 1, "onepass": 2}
+DUMP_BYTES = 64_000_000    # --dump-outputs writes at most this much
 CONFIGS = {
     # name: (keys, leaves, spec, dataset, dtype, scaling)
     "M": (200_000_000, 1 << 20, "linear,linear", "uniform", "uint64", None),
@@ -69,11 +76,15 @@ def parse_args():
     ap.add_argument("--dtype", default=None, choices=["uint64", "uint32"])
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
     ap.add_argument("--mode", default="exact", choices=sorted(MODES))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (side figures, CPU baseline, parity, other configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB: a seeded sample of the leaves above)")
     ap.add_argument("--cpu-sample", type=int, default=200_000_000,
-                    help="keys of the workload the CPU baseline is timed on (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side figures (fast mode, other configurations, PCIe-inclusive, fast root)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the side figures of the other BASELINE configurations")
+                    help="--full: keys of the workload the CPU baseline is timed on (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity checks against the oracle")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the side figures (fast mode, other configurations, PCIe-inclusive, fast root)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the side figures of the other BASELINE configurations")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL; gloo for functional tests)")
     ap.add_argument("--exchange", default=None, choices=["rccl", "direct", "auto"],
                     help="N>1: how the rows reach every rank -- ncclAllGather, direct peer stores over xGMI (rmi_hip_peer_*), or (default "
@@ -199,6 +210,25 @@ def parity_against(o, g, what):
         "avg_l2_rel_diff": abs(float(g.model_avg_l2_error) - float(o.model_avg_l2_error)) / max(1e-300, abs(float(o.model_avg_l2_error))),
         "avg_log2_rel_diff": abs(float(g.model_avg_log2_error) - float(o.model_avg_log2_error)) / max(1e-300, abs(float(o.model_avg_log2_error))),
     }
+
+
+def dump_outputs(out_dir, per_leaf, aggregates, limit=DUMP_BYTES):
+    """--dump-outputs: every array of `per_leaf` (first axis = leaf) and the model's `aggregates` as out_dir/<name>.npy in float64
+    (the integers are below 2^53: exact).  Should the leaf arrays exceed `limit` bytes, the same seeded sample of leaves is taken
+    from each, and their indices are written as leaf_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    L = len(next(iter(per_leaf.values())))
+    width = sum(a.size // L for a in per_leaf.values())                  # float64 values a leaf, over all arrays
+    room = (limit - 8 * len(aggregates) - 4096) // 8                     # (4 KB: the files' headers)
+    idx = None
+    if L * width > room:
+        idx = np.sort(np.random.default_rng(0).choice(L, room // (width + 1), replace=False))
+        np.save(os.path.join(out_dir, "leaf_index.npy"), idx.astype(np.float64))
+    for name, a in per_leaf.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if idx is None else a[idx], dtype=np.float64))
+    if aggregates:
+        np.save(os.path.join(out_dir, "aggregates.npy"), np.array(aggregates, dtype=np.float64))
 
 
 def time_steps(step, n, warm=3):
@@ -455,7 +485,8 @@ def main():
         else:
             tr.generate_keys(args.dataset, np_dtype, n_global, 0, n_global)
         t0 = time.perf_counter()
-        keys_np = tr.download_keys()
+        if args.full:
+            keys_np = tr.download_keys()               # (the host copy the CPU baseline and the PCIe-inclusive figures take)
         root = tr.fit_root(root_kind, L_global)        # exact (reference-order) root fit
         root_s = time.perf_counter() - t0
         tr.set_fit_mode(mode)
@@ -494,7 +525,8 @@ def main():
     # the box's own streaming read rate, measured in this run on the resident key array (a read-only kernel,
     # non-temporal 16-byte loads): what "HBM-bound" can mean on this machine, beside the 8 TB/s of the data sheet.  It runs
     # HERE, in front of the warm-up: the exact root fit before it keeps the host busy for ~1 s with the GPU idle, and a device
-    # that has dropped to its low-power state needs more than W = 5 steps of 0.5 ms to be back at its clocks.
+    # that has dropped to its low-power state needs more than W = 5 steps of 0.5 ms to be back at its clocks.  A plain run
+    # reports no figure of it but keeps the passes (~20 ms): without them its 20 / 5 steps measured 1-4 % slower.
     measured_bw, measured_bw_stride, measured_bw_err = None, None, None
     if world == 1:
         try:
@@ -568,8 +600,22 @@ def main():
         path_gbs = b_leaf / dev_s / 1e9 if dev_s > 0 else 0.0
         dom_s = kernel_us[dom] * 1e-6
         dom_gbs = b_leaf / dom_s / 1e9 if dom_s > 0 else 0.0
-        # (the timed trainings' arrays, through the wrapper: one more training of the same configuration, before any other one)
-        g_head = tr.train_leaves(root, leaf_kind, L_global).materialize() if world == 1 else None
+        # the last timed step's arrays, through the wrapper (they stay in the context until its next training)
+        g_head = None
+        if world == 1 and (args.full or args.dump_outputs):
+            g_head = tr._result(res, root, leaf_kind, L_global).materialize()
+        if args.dump_outputs:
+            if g_head is not None:
+                dump_outputs(args.dump_outputs,
+                             {"leaf_params": g_head.leaf_params, "leaf_max_error": g_head.last_layer_max_l1s,
+                              "leaf_count": g_head.leaf_counts, "leaf_start": g_head.leaf_starts[:-1]},
+                             [g_head.model_avg_error, g_head.model_avg_l2_error, g_head.model_avg_log2_error, g_head.model_max_log2_error,
+                              g_head.model_max_error, g_head.model_max_error_idx])
+            else:                                         # N > 1: the row table every rank holds (params..., error) per leaf
+                rows = sh.full_rows()
+                w = rows.size // L_global // 8
+                dump_outputs(args.dump_outputs, {"leaf_params": rows.view(np.float64).reshape(L_global, w)[:, :w - 1],
+                                                 "leaf_max_error": rows.view(np.uint64).reshape(L_global, w)[:, w - 1]}, [])
         mode_text = {
             0: ("exact, key-parallel one-read kernel for linear_spline leaves (k_spline_scan): bucketing scan, the containers' end points, the error "
                 "pass and the leaf ends in one pass over coalesced 16-byte loads; no recurrence, coefficients bit-identical") if scan_path else
@@ -625,7 +671,7 @@ def main():
                 out["exchange_ab"] = sh.auto_report
         tag = args.config.lower() + ("_dups" if args.dataset == "dups" and args.config == "C5" else "")
         tpath = traffic_file(tag)
-        if os.path.exists(tpath) and world == 1 and not used:
+        if args.full and os.path.exists(tpath) and world == 1 and not used:
             try:
                 tj = json.load(open(tpath))
                 # the counters were taken on a build of these very sources, or the figure is not quoted
@@ -642,7 +688,7 @@ def main():
             except Exception:
                 pass
 
-        if world == 1:
+        if world == 1 and args.full:
             bw = measured_bw
             if bw:
                 out["roofline"]["measured_peak"] = float(bw)
@@ -656,9 +702,10 @@ def main():
             else:
                 out["roofline"]["measured_peak"] = None
                 out["roofline"]["measured_peak_note"] = "failed: " + str(measured_bw_err)
-        out["env"] = env_info(torch)
+        if args.full:
+            out["env"] = env_info(torch)
         # the driver's flags give a 12 ms timed region; the same steps once more over 200 (the protocol of profiles/)
-        if world == 1 and args.steps < 200 and not args.no_extras:
+        if world == 1 and args.full and args.steps < 200 and not args.no_extras:
             tr.set_profile_level(-1)
             for _ in range(20):
                 run_step()
@@ -675,7 +722,7 @@ def main():
         def frac_of(nkeys, kbytes, L, rowb, dsec):
             return (nkeys * kbytes + rowb * L) / dsec / 1e9 / HBM_PEAK_GBS if dsec > 0 else 0.0
 
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             tr.set_profile_level(0)
             if not used and leaf_kind == 0:
                 # the sufficient-statistics mode beside it (SURVEY H2's fast mode): one read of the keys, integers through
@@ -781,7 +828,7 @@ def main():
                                               "note": "root fitted on the GPU from parallel sums (opt-in, coefficients within ~1e-12 of the "
                                                       "exact fit, not bit-identical) + the leaf path of THAT root; not the headline value"}
         o_head = None
-        if not args.no_cpu_baseline and args.cpu_sample > 0 and world == 1 and keys_np is not None:
+        if args.full and not args.no_cpu_baseline and args.cpu_sample > 0 and world == 1 and keys_np is not None:
             sample = keys_np[: min(args.cpu_sample, len(keys_np))]
             o_head, L_cpu, out["cpu_baseline"] = cpu_baseline(sample, args.spec, L_global, n_global)
             # ---- the three output clauses, measured for the mode `value` is quoted in
@@ -795,8 +842,8 @@ def main():
                 t2.close()
         else:
             out["cpu_baseline"] = None
-        # ---- the other BASELINE configurations on this GPU, as side figures of the default run
-        if world == 1 and args.config == "M" and not args.no_extras and not args.no_configs:
+        # ---- the other BASELINE configurations on this GPU, as side figures of the --full run
+        if world == 1 and args.full and args.config == "M" and not args.no_extras and not args.no_configs:
             out["configs"] = side_configs(T, tr, local_rank, not args.no_cpu_baseline)
         print(json.dumps(out))
     if dist is not None:

@@ -1,7 +1,7 @@
 """Calibrate the guard bound of the sufficient-statistics mode against the oracle (CPU only)."""
-import ctypes as C, sys, time
+import ctypes as C, os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from oracle import binding as orc
 from rmi_amd import datagen
 
