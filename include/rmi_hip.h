@@ -420,6 +420,60 @@ int rmi_hip_download_checked(rmi_hip_ctx* ctx, int what, uint64_t generation, vo
 /* Device pointer of the packed rows (for an all-gather over RCCL without a host bounce). */
 void* rmi_hip_device_rows(rmi_hip_ctx* ctx);
 
+/* ---- querying a trained RMI on the device (additive; the ABI version stays 6) ----
+ * A device index holds a copy of a two-layer model -- root parameters, the packed rows (params..., err) and a radix-table
+ * root's hint table -- in device memory of its own, so it outlives later trainings on the context.  For a batch of query
+ * keys in device memory it answers:
+ *   rmi_hip_index_lookup  (guess, err) per query, bit-identical to the emitted C++ `lookup(key, &err)` (codegen.rs:621-717):
+ *                         the root function, modelIndex (FCLAMP for roots with a bounds check, the raw prediction for
+ *                         cubic / radix / radix tables / bradix), the leaf's std::fma, *err = row[ppl], FCLAMP(fpred, n - 1.0).
+ *   rmi_hip_index_search  pos = lower_bound(keys, q) over the context's resident keys, for every query (absent keys and
+ *                         keys outside the key range included): the window [guess - err, guess + err] clamped to [0, n],
+ *                         then a galloping search outward from the window's edge when the lower bound lies outside it.
+ *   rmi_hip_index_verify  search with the resident keys as the queries and no positions: the reference's acceptance loop
+ *                         (the main.cpp of the reference's tests), checked = n, outside = the keys with |lookup - lower_bound| > err.
+ * Where the emitted C++ has no defined result the device defines one and counts the query in `root_oob`:
+ *   - a root without a bounds check whose raw prediction lies outside [0, L): the leaf index is clamped to [0, L-1];
+ *   - a NaN root prediction (f64 queries): leaf 0.  A NaN leaf prediction gives guess 0 (Rust's saturating `as u64`).
+ * A model without error rows (errors == NULL, the emitted `--no-errors` code) has err = 0 for every leaf: search gallops
+ * from the guess, lookup writes no err.  Bounded RMIs (cache_fix) are not indexed (RMI_ERR_UNSUPPORTED_MODEL at the
+ * caller that knows the model is bounded: the rows alone do not say so).
+ * All pointers named d_* are device pointers; the calls run on the context's stream (rmi_hip_set_stream).  lookup with
+ * st == NULL and search with st == NULL return without synchronising; with st the call waits for its kernel and fills it.
+ * nq == 0 is a no-op.  search and verify return RMI_ERR_BAD_ARG when the context's resident key count differs from the
+ * index's num_rows or the query dtype differs from the index's; lookup only checks the dtype.  An index never touches the
+ * context's per-leaf arrays: rmi_hip_download_* return the last training's results as before.  rmi_hip_destroy frees the
+ * indexes of a context that are still alive (their handles are invalid afterwards).  One index is used by one thread. */
+typedef struct rmi_hip_index rmi_hip_index;
+typedef struct {
+  uint64_t queries;
+  uint64_t fallbacks;   /* queries whose lower bound lay outside [guess - err, guess + err] (search / verify) */
+  uint64_t root_oob;    /* queries with a raw root prediction outside [0, L) or NaN (see above) */
+  uint64_t device_ns;   /* hipEvent time of the kernel */
+} rmi_hip_search_stats;
+/* From the training `generation` (rmi_hip_result.generation) of the context: rows and radix table copied device to device.
+ * RMI_ERR_BAD_ARG if the context has trained again since, or the training was one shard of a sharded model. */
+int rmi_hip_index_from_result(rmi_hip_ctx* ctx, const rmi_hip_model_params* root, uint64_t generation, rmi_hip_index** out);
+/* From host arrays: leaf params num_leaves * ppl f64, errors num_leaves u64 or NULL (no error rows), root_table: a radix-table
+ * root's hint table (table_entries = 2^table_bits) or NULL.  num_rows: the key count the model was trained on (n). */
+int rmi_hip_index_from_arrays(rmi_hip_ctx* ctx, const rmi_hip_model_params* root, int leaf_kind, uint64_t num_leaves,
+                              uint64_t num_rows, int dtype, const double* params, const uint64_t* errors,
+                              const uint32_t* root_table, uint64_t table_entries, rmi_hip_index** out);
+int rmi_hip_index_lookup(rmi_hip_ctx* ctx, const rmi_hip_index* ix, const void* d_queries, uint64_t nq, int dtype,
+                         uint64_t* d_guess, uint64_t* d_err /* NULL ok */, rmi_hip_search_stats* st /* NULL ok */);
+int rmi_hip_index_search(rmi_hip_ctx* ctx, const rmi_hip_index* ix, const void* d_queries, uint64_t nq, int dtype,
+                         uint64_t* d_pos /* NULL: count only */, rmi_hip_search_stats* st /* NULL ok */);
+int rmi_hip_index_verify(rmi_hip_ctx* ctx, const rmi_hip_index* ix, uint64_t* checked, uint64_t* outside);
+/* The search variant: 0 = one query per lane (branchless bisection of the window, the last 128-byte line of keys read at
+ * once; the default), 1 = eight lanes per query (eight probes a round).  See DESIGN.md for the measurements. */
+int rmi_hip_index_set_variant(rmi_hip_index* ix, int variant);
+void rmi_hip_index_destroy(rmi_hip_index* ix);
+/* Device memory on the context's device, e.g. to stage a batch of queries from host memory through the context's HIP
+ * runtime; rmi_hip_copy is a synchronous hipMemcpyDefault on the context's stream (either side host or device). */
+int rmi_hip_device_alloc(rmi_hip_ctx* ctx, uint64_t bytes, void** d_out);
+int rmi_hip_device_free(rmi_hip_ctx* ctx, void* d_ptr);
+int rmi_hip_copy(rmi_hip_ctx* ctx, void* dst, const void* src, uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

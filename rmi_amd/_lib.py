@@ -42,6 +42,10 @@ class Result(C.Structure):
     ]
 
 
+class SearchStats(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("fallbacks", C.c_uint64), ("root_oob", C.c_uint64), ("device_ns", C.c_uint64)]
+
+
 # every symbol include/rmi_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("rmi_hip_abi_version", C.c_int, []),
@@ -110,6 +114,18 @@ SYMBOLS = [
     ("rmi_hip_peer_import", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     ("rmi_hip_set_exchange", C.c_int, [C.c_void_p, C.c_int]),
     ("rmi_hip_download_rows_full", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("rmi_hip_index_from_result", C.c_int, [C.c_void_p, C.POINTER(ModelParams), C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("rmi_hip_index_from_arrays", C.c_int, [C.c_void_p, C.POINTER(ModelParams), C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("rmi_hip_index_lookup", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(SearchStats)]),
+    ("rmi_hip_index_search", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(SearchStats)]),
+    ("rmi_hip_index_verify", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rmi_hip_index_set_variant", C.c_int, [C.c_void_p, C.c_int]),
+    ("rmi_hip_index_destroy", None, [C.c_void_p]),
+    ("rmi_hip_device_alloc", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("rmi_hip_device_free", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rmi_hip_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
 ]
 
 KEY_AT_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p, C.c_uint64)

@@ -1,7 +1,8 @@
 """In-tree build of the gfx950 HIP library (hipcc cross-compiles without a GPU).
 
-Two translation units, compiled to objects under rmi_amd/build/ (git-ignored) and linked into rmi_amd/librmi_hip.so:
-rmi_hip.hip (the C ABI, the host orchestration and the kernels of pipelines 1-4) and rmi_scan.hip (pipeline 5)."""
+Three translation units, compiled to objects under rmi_amd/build/ (git-ignored) and linked into rmi_amd/librmi_hip.so:
+rmi_hip.hip (the C ABI, the host orchestration and the kernels of pipelines 1-4), rmi_scan.hip (pipeline 5) and
+rmi_lookup.hip (the device index: lookup, search, verify)."""
 from __future__ import annotations
 
 import os
@@ -15,8 +16,10 @@ SO = os.path.join(HERE, "librmi_hip.so")
 COMMON = ["rmi_kernels.hip.h", "rmi_stream.hip.h", "rmi_sigma.hip.h", "rmi_lanes.hip.h", "rmi_device.hip.h", "rmi_scan_launch.h"]
 # source -> the headers it includes (besides COMMON)
 UNITS = {
-    "rmi_hip.hip": ["rmi_regs.hip.h", "rmi_regs_block.inc.h", "rmi_regs_replay.inc.h", "rmi_multi.inc.h", "rmi_root_host.h", "../../include/rmi_hip.h"],
+    "rmi_hip.hip": ["rmi_regs.hip.h", "rmi_regs_block.inc.h", "rmi_regs_replay.inc.h", "rmi_multi.inc.h", "rmi_root_host.h",
+                    "rmi_lookup_launch.h", "../../include/rmi_hip.h"],
     "rmi_scan.hip": ["rmi_scan.hip.h", "rmi_scan_ends.inc.h"],
+    "rmi_lookup.hip": ["rmi_lookup_launch.h", "../../include/rmi_hip.h"],
 }
 SOURCES = list(UNITS)
 HEADERS = sorted(set(COMMON + [h for hs in UNITS.values() for h in hs]))

@@ -44,6 +44,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-s", "--stats-file", metavar="file", help="accepted for compatibility (unused in the reference too)")
     ap.add_argument("--fast-root", action="store_true",
                     help="(extension) fit linear / robust_linear roots from parallel sums on the GPU: not bit-identical to the reference")
+    ap.add_argument("--verify", action="store_true",
+                    help="after a single training, check |lookup(key) - lower_bound(key)| <= err for every key on the device")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -128,6 +130,12 @@ def main(argv=None) -> int:
         if not args.no_code:
             codegen.output_rmi(args.namespace, rmi, args.data_path, key_type=key_c, include_errors=not args.no_errors,
                                build_time_ns=0 if args.zero_build_time else None)
+        if args.verify:                                                                # the acceptance loop of the reference's tests
+            ix = rmi.index()
+            checked, outside = ix.verify()
+            ix.close()
+            print(f"checked {checked} keys, {outside} outside the bound")
+            return 1 if outside else 0
         return 0
     except train.RMIError as e:
         print(f"error: {e}", file=sys.stderr)

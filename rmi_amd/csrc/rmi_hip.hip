@@ -24,6 +24,7 @@
 #include "rmi_lanes.hip.h"
 #include "rmi_regs.hip.h"
 #include "rmi_scan_launch.h"
+#include "rmi_lookup_launch.h"
 #include "rmi_root_host.h"
 
 using namespace rmi;
@@ -189,6 +190,7 @@ struct rmi_hip_ctx {
   int upload_rc = RMI_OK;
   bool defer_sync = false;                      // rmi_hip_train_sharded: the caller queues the exchange, synchronises and finishes
   struct rmi_hip_multi* multi = nullptr;        // multi-GPU state (rmi_multi.inc.h)
+  std::vector<rmi_hip_index*> indexes;          // device indexes built on this context (rmi_lookup.hip), freed with it
   std::string err;
 };
 
@@ -217,6 +219,22 @@ static void set_err(rmi_hip_ctx* c, const char* fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
   if (c) c->err = buf;
 }
+
+namespace rmi {
+void ctx_lookup_view(const rmi_hip_ctx* c, CtxLookupView* v) {
+  v->device = c->device; v->stream = c->stream; v->keys = c->d_keys; v->n = c->n; v->dtype = c->dtype; v->n_cu = c->n_cu;
+  v->generation = c->generation;
+  // the rows of a shard or of a streamed training are not the whole model of this context's keys
+  v->last_L = (c->have_shard || c->stream_mode) ? 0 : c->last_L;
+  v->last_ppl = c->last_ppl; v->rows = c->last_rows;
+  v->table = c->d_table; v->table_entries = c->d_table ? c->h_table.size() : 0;
+}
+void ctx_set_error(rmi_hip_ctx* c, const char* msg) { if (c) c->err = msg; }
+void ctx_register_index(rmi_hip_ctx* c, rmi_hip_index* ix, bool add) {
+  auto& v = c->indexes;
+  if (add) v.push_back(ix); else v.erase(std::remove(v.begin(), v.end(), ix), v.end());
+}
+}  // namespace rmi
 
 #define HIPCHK(ctx, call)                                                                   \
   do {                                                                                      \
@@ -394,6 +412,8 @@ void rmi_hip_destroy(rmi_hip_ctx* c) {
   if (!c) return;
   for (rmi_hip_ctx* v : c->many_views) rmi_hip_destroy(v);
   c->many_views.clear();
+  for (rmi_hip_index* ix : c->indexes) index_release(ix);
+  c->indexes.clear();
   if (c->upload_thread.joinable()) c->upload_thread.join();
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);

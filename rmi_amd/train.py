@@ -156,6 +156,11 @@ class TrainedRMI:
         """Byte image of the reference's L1_PARAMETERS file (codegen.rs:288-315)."""
         return self._get("rows")
 
+    def index(self):
+        """A device index of this model over the trainer's resident keys (rmi_amd.index.DeviceIndex)."""
+        from .index import DeviceIndex
+        return DeviceIndex.from_trained(self)
+
 
 class Trainer:
     """Owns one device context with the key array resident in HBM (the role of
