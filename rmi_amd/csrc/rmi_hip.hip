@@ -26,21 +26,20 @@
 #include "rmi_scan_launch.h"
 #include "rmi_lookup_launch.h"
 #include "rmi_root_host.h"
+#include "rmi_route.h"
 
 using namespace rmi;
 
 struct rmi_hip_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
+  hipStream_t own_stream = nullptr, stream = nullptr;
   // keys
   const void* d_keys = nullptr;
   void* d_keys_owned = nullptr;
   uint64_t n = 0;
   int dtype = RMI_KEY_U64;
   // outputs (capacity in leaves)
-  uint64_t cap_leaves = 0;
-  int cap_ppl = 0;
+  uint64_t cap_leaves = 0; int cap_ppl = 0;
   unsigned long long* d_leaf_start = nullptr;   // L+1
   double* d_params = nullptr;                   // L*ppl
   unsigned long long* d_maxerr = nullptr;       // L
@@ -51,14 +50,11 @@ struct rmi_hip_ctx {
   unsigned long long* d_tilemin = nullptr;
   // radix-table root (radix8/18/22/26/28): hint_table of the last rmi_hip_fit_root / rmi_hip_set_root_table
   std::vector<uint32_t> h_table;
-  uint32_t* d_table = nullptr;
-  uint64_t d_table_cap = 0;
+  uint32_t* d_table = nullptr; uint64_t d_table_cap = 0;
   std::vector<uint64_t> h_spline;               // last rmi_hip_cache_fix result, (key, offset) pairs
-  double* d_cube = nullptr;                     // cubic leaves: span, then pow(span, 3.0), per leaf
-  uint64_t cube_cap = 0;
+  double* d_cube = nullptr; uint64_t cube_cap = 0;   // cubic leaves: span, then pow(span, 3.0), per leaf
   std::vector<double> h_cube;
-  unsigned long long* d_long = nullptr;         // long-leaf hand-over list (pass A -> k_fit_long)
-  uint64_t long_cap = 0;
+  unsigned long long* d_long = nullptr; uint64_t long_cap = 0;   // long-leaf hand-over list (pass A -> k_fit_long)
   DevState* d_state = nullptr;
   StatsPartial* d_partials = nullptr;           // per-block aggregate records of k_finalize
   DevState* h_state = nullptr;                  // pinned
@@ -75,7 +71,9 @@ struct rmi_hip_ctx {
   int stream_slot = 0;
   void* h_stage[2] = {nullptr, nullptr};        // pinned staging buffers of the chunked upload
   hipStream_t copy_stream = nullptr;
-  bool opt_tail = true;                         // k_lane_reduce publishes the result behind k_leaf_lanes; the list kernels run behind the synchronisation, and only if a leaf was handed over
+  rmi_route::Knobs knobs;                       // the environment's settings (rmi_route.h)
+  rmi_route::RouteMemory mem;                   // what the last trainings taught about the key set
+  rmi_route::Route last_route;                  // the route of the last training
   bool tail_armed = false;
   std::function<int()> tail_fn;                 // the list kernels + k_finalize_listed of the last launch (listed_epilogue)
   std::function<int(unsigned int)> regs_listed_fn;          // pipeline 4: k_leaf_lanes_listed + k_lane_reduce once more, run behind the synchronisation and only if k_leaf_regs listed a group
@@ -88,58 +86,28 @@ struct rmi_hip_ctx {
   hipEvent_t ev[10] = {};
   int profile_level = 0;                        // -1: no events at all (device_ns = 0); 0: whole call only; 1: + the first (dominant) kernel; 2: every kernel group
   DevState* h_state_dev = nullptr;              // device address of the pinned h_state (written by the last kernel)
-  int pipeline = 3;                             // 1 = one kernel per reference pass; 2 = streaming passes A/B; 3 = leaf-lane kernels (rmi_lanes.hip.h)
   double* d_lntab = nullptr;                    // RN(1 / k) for the running count of the leaf-lane walk (k_lane_table)
-  bool lanes_fuse = true;                       // error pass fused behind the fit in k_leaf_lanes (else k_err_range)
   // pipeline 4 (rmi_regs.hip.h): k_leaf_regs -- one read of the keys, a leaf's keys stay in registers between its fit and its error pass --
   // in place of k_leaf_lanes where the leaves are short enough on average; the groups it does not take go through k_leaf_lanes_listed
-  bool regs = true;                             // RMI_HIP_REGS=0: k_leaf_lanes for everything
-  int regs_u32 = 2;                             // 4-byte keys through k_leaf_regs: 2 = two waves per SIMD with the raw keys stashed (k_leaf_regs<K, 2>), 1 = the
-                                                // one-wave kernel in half-line panels, 0 = k_leaf_lanes (RMI_HIP_REGS_U32)
-  bool regs_forced = false;                     // RMI_HIP_REGS=1: k_leaf_regs wherever it applies, whatever the number of groups
-  unsigned int regs_grid = 0;                   // persistent waves of k_leaf_regs (0: 4 per CU)
-  unsigned int regs_max_avg = 208;              // average keys per leaf above which most groups would not fit (RG_MAXPTS = 240 per container)
-  unsigned int regs_long_max_avg = 640;         // ... and up to which k_leaf_regs<K, LONG> takes them (the steps behind the stash through the ring twice); above: k_leaf_lanes
-  static constexpr unsigned int regs_slow = 0;  // (debugging aid of round 4: every group on the list)
-  bool regs_backoff = true;                     // RMI_HIP_REGS_BACKOFF=0: k_leaf_regs also for key sets on which it listed most groups last time
-  uint64_t regs_off_epoch = 0; uint64_t regs_off_L[8] = {}; int regs_off_n = 0;   // ... the (key set, leaves) pairs remembered
-  static constexpr bool regs_queue = false;     // (groups dealt to the waves from a counter instead of by wave number: measured 473 against 460 us; the switch is gone)
   double* d_regtab = nullptr;                   // the interleaved step table of k_leaf_regs
   unsigned long long* d_regprof = nullptr;      // RG_PROF builds: cycles per phase, summed over the waves
   std::vector<rmi_hip_ctx*> many_views;         // rmi_hip_train_many: contexts that borrow this one's keys (kept for the next call)
-  void* d_bnext = nullptr;                      // the keys on either side of every leaf, for k_regs_finalize: [2][64 groups]
-  unsigned char* d_tile_slow = nullptr;         // per group: finished by k_leaf_lanes_listed
-  unsigned int* d_slow_list = nullptr;          // groups of 64 leaves left to k_leaf_lanes_listed (counter: d_tickets[1])
-  uint64_t slow_cap = 0;
+  void* d_bnext = nullptr; uint64_t bnext_cap = 0;   // the keys on either side of every leaf, for k_regs_finalize: [2][64 groups]
+  unsigned char* d_tile_slow = nullptr; uint64_t tile_slow_cap = 0;   // per group: finished by k_leaf_lanes_listed
+  unsigned int* d_slow_list = nullptr; uint64_t slow_cap = 0;   // groups of 64 leaves left to k_leaf_lanes_listed (counter: d_tickets[1])
   int n_cu = 256;
-  bool last_regs = false;
   void* d_gaps = nullptr;                       // pipeline 5: the listed stretches of empty leaves (GapRec)
-  uint64_t scan_hint_epoch = 0, scan_hint_L = 0; unsigned int scan_hint_n = ~0u;   // ... and how many it left the last time (key set, leaves per launch)
-  uint64_t scan_skew_epoch = ~0ull, scan_skew_L = 0;   // (key set, leaves) whose short form listed hundreds of tiles: a skewed key set -- its next trainings take the long-leaf instance
-  unsigned int* d_tile_list = nullptr;          // ... the tiles the short form's kernel leaves to the general form's
-  uint64_t tile_list_cap = 0;
-  // pipeline 5 writes the rows (codegen.rs:288-315: alpha, beta, error -- the 24 L bytes of SURVEY 8d) and the bucket table only; the separate
-  // coefficient / error / count arrays hold the same values and are filled from them when somebody downloads one (k_lean_arrays)
-  bool lean = true;                             // RMI_HIP_LEAN=0: the kernel writes all five arrays
-  bool last_lean = false, lean_derived = false;
+  unsigned int* d_tile_list = nullptr; uint64_t tile_list_cap = 0;   // ... the tiles the short form's kernel leaves to the general form's
+  // pipeline 5 writes the rows (codegen.rs:288-315: alpha, beta, error -- the 24 L bytes of SURVEY 8d) and the bucket table only (Route::lean); the
+  // separate coefficient / error / count arrays hold the same values and are filled from them when somebody downloads one (k_lean_arrays)
+  bool lean_derived = false;
   unsigned long long lean_last_target = ~0ull, lean_leaf_lo = 0;   // (of the training the arrays belong to: the shard may be gone when they are asked for)
-  bool last_scan = false;
-  unsigned int scan_waves = 0;                  // its persistent waves per kernel at most (0: as many as the device holds, rmi_scan_waves_per_cu)
-  bool lanes_search = true;                     // leaf boundaries by k_leaf_search where the root allows it (else the bucketing scan)
-  uint64_t edge_epoch = 0;                      // first / last resident key of the key set `keys_epoch` (radix roots: is the prefix common?)
-  uint64_t edge_first = 0, edge_last = 0;
-  uint64_t edgef_epoch = 0;                     // ... as doubles (cubic roots: is the polynomial increasing between them?)
-  double edge_first_f = 0.0, edge_last_f = 0.0;
-  bool cubic_margin = true;                     // RMI_HIP_CUBIC_MARGIN=0: cubic roots always with the per-key verification (k_leaf_lanes, pipeline 3)
-  double cubic_margin_scale = 1.0;              // testing: RMI_HIP_CUBIC_MARGIN_SCALE widens the margin (1e13: every leaf is verified key by key)
-  bool last_lanes = false;
+  // first / last resident key, as integers and as doubles; the key set the radix fact (is the prefix common?) / the cubic fact (is the
+  // polynomial increasing between them?) last read them for
+  uint64_t edge_first = 0, edge_last = 0, edge_epoch = 0, edgef_epoch = 0; double edge_first_f = 0.0, edge_last_f = 0.0;
   // giant leaves (containers of more than host_min points): recorded by k_list, fitted on host cores after the device
   // pipeline, their error pass and finalize in a short epilogue (giant_epilogue).  Plain single-context trainings only.
-  GiantLeaf* d_giant = nullptr;
-  uint64_t giant_cap = 0;
-  uint64_t host_min = 262144;                   // RMI_HIP_HOST_MIN; 0: never.  (A wave walks 262 144 points in ~7 ms, a host core in ~1: below that the
-                                                //  leaves of a skewed key set are many and run side by side on the device)
-  bool host_min_set = false;                    // RMI_HIP_HOST_MIN given: the threshold alone decides (else giant leaves only where the AVERAGE leaf is far below it)
+  GiantLeaf* d_giant = nullptr; uint64_t giant_cap = 0;
   bool giant_armed = false;                     // the last launch recorded giant leaves for the host
   // the giant list early (k_giant_scan in front of k_list, read through pinned memory): the host walks the chains while
   // the device fits the other listed leaves
@@ -152,36 +120,21 @@ struct rmi_hip_ctx {
   std::vector<double> giant_ab;
   struct { const void* keys; Span sp; uint64_t L; unsigned long long* leaf_start; double* params; unsigned long long* maxerr; unsigned long long* run;
            unsigned long long* err; unsigned long long* count; unsigned char* rows; uint64_t waves; } lp = {};
-  uint64_t fit_threads = 131072;                // lanes of pass A (256 CUs x 8 waves x 64)
   uint64_t err_threads = 262144;                // lanes of pass B (4 waves/SIMD)
-  int fit_min_chunk = 64;
   bool robust_leaf = false;                     // this call's leaves are robust_linear (fitted by k_fit_leaf; predict like linear)
-  unsigned int long_min = 4096;                 // leaves with more points go to k_fit_long (>= FS_TMAX)
   // fit mode of linear leaves: 0 = exact (two streaming passes), 1 = one pass from sufficient statistics with the
   // guard (error integers bit-identical, flagged leaves re-fitted exactly), 2 = one pass, guard only counted
   int fit_mode = 0;
   double guard_k = 2.0;
   uint64_t sigma_waves = 4096;                  // k_sigma2: chunks the keys are cut into (one wave each)
-  unsigned int sigma_min_leaf = 32;             // average keys per leaf below which the exact kernels are used
   unsigned int* d_flist = nullptr;              // leaves handed to the exact kernels: SG_REGIONS regions of flist_cap ids ...
   unsigned long long* d_flist_cnt = nullptr;    // ... and their counters
-  void* d_recs = nullptr;                       // one-pass mode 2: partial sums of long leaves, [blocks][rpw] + the counts
-  uint64_t recs_bytes = 0;
-  unsigned long long* d_segs = nullptr;         // one-pass modes: the stretches of the long listed leaves for their error pass
-  uint64_t segs_cap = 0;
+  void* d_recs = nullptr; uint64_t recs_bytes = 0;   // one-pass mode 2: partial sums of long leaves, [blocks][rpw] + the counts
+  unsigned long long* d_segs = nullptr; uint64_t segs_cap = 0;   // one-pass modes: the stretches of the long listed leaves for their error pass
   SgParams last_sg;                             // the parameters of the last k_sigma2 launch (k_list reads the records)
-  // A key set on which the one-pass kernel hands most leaves to the exact list kernels (duplicate-heavy keys; keys
-  // whose f64 images collapse, in the guarded mode) is served faster by the exact streaming passes: 1.1 ms against
-  // 13.8 ms on 200 M duplicate-heavy keys.  Remembered per (key set, leaf count, mode); the next call takes the exact path.
-  uint64_t keys_epoch = 1;                      // bumped whenever the context gets new keys
-  uint64_t hint_epoch = 0;                      // the key set the remembered leaf counts belong to
-  uint64_t hint_L[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (a parameter grid trains several leaf counts on one key set)
-  int hint_n = 0, hint_mode = -1;
-  void* d_bkeys = nullptr;                      // one-pass mode: key[e] and key[s-1] of every leaf (2 x leaves keys), see k_finalize
-  uint64_t bkeys_cap = 0;
+  uint64_t keys_epoch = 1;                      // bumped whenever the context gets new keys (the key set RouteMemory remembers things of)
+  void* d_bkeys = nullptr; uint64_t bkeys_cap = 0;   // one-pass mode: key[e] and key[s-1] of every leaf (2 x leaves keys), see k_finalize
   uint64_t flist_cap = 0;                       // entries per region
-  bool last_sigma = false;
-  bool last_spline = false;                     // ... for linear_spline leaves (bit-identical in one pass)
   // last result
   uint64_t last_L = 0;
   int last_ppl = 2;
@@ -245,10 +198,21 @@ void ctx_register_index(rmi_hip_ctx* c, rmi_hip_index* ix, bool add) {
     }                                                                                       \
   } while (0)
 
+// A buffer of the context that grows with the work (its contents are not kept): room for `need` elements of `bytes` each.
+template <typename T> static void release(T*& p, uint64_t& cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+template <typename T>
+static int grow(rmi_hip_ctx* c, T*& p, uint64_t& cap, uint64_t need, uint64_t bytes) {
+  if (cap >= need) return RMI_OK;
+  release(p, cap);
+  HIPCHK(c, hipMalloc(&p, need * bytes));
+  cap = need;
+  return RMI_OK;
+}
+
 extern "C" {
 
 int rmi_hip_abi_version(void) { return RMI_HIP_ABI_VERSION; }
-int rmi_hip_last_pipeline(rmi_hip_ctx* c) { return !c ? RMI_ERR_BAD_ARG : (c->last_scan ? 5 : c->last_regs ? 4 : (c->last_lanes ? 3 : 2)); }
+int rmi_hip_last_pipeline(rmi_hip_ctx* c) { return !c ? RMI_ERR_BAD_ARG : c->last_route.pipeline; }
 
 int rmi_hip_device_count(void) {
   int n = 0;
@@ -355,21 +319,7 @@ int rmi_hip_create(int device_id, rmi_hip_ctx** out) {
   if (hipHostMalloc((void**)&c->h_sentinel, 64, hipHostMallocDefault) != hipSuccess) { rmi_hip_destroy(c); return RMI_ERR_HIP; }
   for (auto& e : c->ev) if (hipEventCreate(&e) != hipSuccess) { rmi_hip_destroy(c); return RMI_ERR_HIP; }
   c->profile_level = 0;                                 // (rmi_hip_set_profile_level)
-  const char* pl = std::getenv("RMI_HIP_PIPELINE");
-  if (pl && *pl) c->pipeline = std::atoi(pl) >= 3 ? 3 : 2;       // 2: the streaming passes of round 2 (what tiny and huge key sets and cubic / robust leaves take anyway); default 3: everything newer
-  { const char* lsr = std::getenv("RMI_HIP_LANES_SEARCH"); if (lsr && *lsr) c->lanes_search = std::atoi(lsr) != 0; }
-  { const char* otl = std::getenv("RMI_HIP_OPT_TAIL"); if (otl && *otl) c->opt_tail = std::atoi(otl) != 0; }
-  { const char* hm = std::getenv("RMI_HIP_HOST_MIN"); if (hm && *hm) { c->host_min = std::strtoull(hm, nullptr, 10); c->host_min_set = true; } }
-  { const char* rg = std::getenv("RMI_HIP_REGS"); if (rg && *rg) { c->regs = std::atoi(rg) != 0; c->regs_forced = c->regs; } }   // (=1 also overrides the choice by group count)
-  { const char* ru = std::getenv("RMI_HIP_REGS_U32"); if (ru && *ru) c->regs_u32 = std::atoi(ru); }
-  { const char* cm = std::getenv("RMI_HIP_CUBIC_MARGIN"); if (cm && *cm) c->cubic_margin = std::atoi(cm) != 0; }
-  { const char* ln = std::getenv("RMI_HIP_LEAN"); if (ln && *ln) c->lean = std::atoi(ln) != 0; }
-  { const char* cm = std::getenv("RMI_HIP_CUBIC_MARGIN_SCALE"); if (cm && *cm) c->cubic_margin_scale = std::atof(cm); }
-  { const char* sc = std::getenv("RMI_HIP_SCAN_WAVES"); if (sc && *sc) c->scan_waves = (unsigned int)std::atoi(sc); }
-  { const char* rg = std::getenv("RMI_HIP_REGS_LONG_MAX_AVG"); if (rg && *rg) c->regs_long_max_avg = (unsigned int)std::atoi(rg); }
-  { const char* rg = std::getenv("RMI_HIP_REGS_GRID"); if (rg && *rg) c->regs_grid = (unsigned int)std::atoi(rg); }
-  { const char* rg = std::getenv("RMI_HIP_REGS_MAX_AVG"); if (rg && *rg) c->regs_max_avg = (unsigned int)std::atoi(rg); }
-  { const char* rg = std::getenv("RMI_HIP_REGS_BACKOFF"); if (rg && *rg) c->regs_backoff = std::atoi(rg) != 0; }
+  c->knobs = rmi_route::read_knobs();
   { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cu > 0) c->n_cu = cu; }
   if (hipMalloc(&c->d_lntab, sizeof(double) * (3 * LN_TMAX + 2 * (LS_SAMPLES + 1))) != hipSuccess) { rmi_hip_destroy(c); return RMI_ERR_HIP; }
   hipLaunchKernelGGL(k_lane_table, dim3((LN_TMAX + 255) / 256), dim3(256), 0, c->stream, c->d_lntab, LN_TMAX);
@@ -377,13 +327,6 @@ int rmi_hip_create(int device_id, rmi_hip_ctx** out) {
   if (RG_PROF) { if (hipMalloc(&c->d_regprof, 128) != hipSuccess || hipMemset(c->d_regprof, 0, 128) != hipSuccess) { rmi_hip_destroy(c); return RMI_ERR_HIP; } }
   hipLaunchKernelGGL(k_regs_table, dim3((RG_TMAX + 255) / 256), dim3(256), 0, c->stream, c->d_regtab, RG_TMAX);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rmi_hip_destroy(c); return RMI_ERR_HIP; }
-  // (the chunk geometry of pass A, pipeline 2: its tests vary it)
-  const char* ft = std::getenv("RMI_HIP_FIT_THREADS");
-  if (ft && *ft) c->fit_threads = std::strtoull(ft, nullptr, 10);
-  const char* fc = std::getenv("RMI_HIP_FIT_MIN_CHUNK");
-  if (fc && *fc) c->fit_min_chunk = std::atoi(fc);
-  const char* lm = std::getenv("RMI_HIP_LONG_MIN");
-  if (lm && *lm) { long v = std::atol(lm); if (v >= 64) c->long_min = (unsigned int)v; }
   *out = c;
   return RMI_OK;
 }
@@ -393,15 +336,10 @@ static void free_outputs(rmi_hip_ctx* c) {
   (void)hipFree(c->d_err); (void)hipFree(c->d_count); (void)hipFree(c->d_rows); (void)hipFree(c->d_tilemin);
   (void)hipFree(c->d_partials); c->d_partials = nullptr;
   (void)hipFree(c->d_tickets); c->d_tickets = nullptr;
-  if (c->d_long) { (void)hipFree(c->d_long); c->d_long = nullptr; c->long_cap = 0; }
-  if (c->d_cube) { (void)hipFree(c->d_cube); c->d_cube = nullptr; c->cube_cap = 0; }
-  if (c->d_flist) { (void)hipFree(c->d_flist); c->d_flist = nullptr; c->flist_cap = 0; }
+  release(c->d_long, c->long_cap); release(c->d_cube, c->cube_cap); release(c->d_flist, c->flist_cap); release(c->d_tile_list, c->tile_list_cap);
+  release(c->d_bkeys, c->bkeys_cap); release(c->d_recs, c->recs_bytes); release(c->d_segs, c->segs_cap);
   if (c->d_flist_cnt) { (void)hipFree(c->d_flist_cnt); c->d_flist_cnt = nullptr; }
   if (c->d_gaps) { (void)hipFree(c->d_gaps); c->d_gaps = nullptr; }
-  if (c->d_tile_list) { (void)hipFree(c->d_tile_list); c->d_tile_list = nullptr; c->tile_list_cap = 0; }
-  if (c->d_bkeys) { (void)hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_cap = 0; }
-  if (c->d_recs) { (void)hipFree(c->d_recs); c->d_recs = nullptr; c->recs_bytes = 0; }
-  if (c->d_segs) { (void)hipFree(c->d_segs); c->d_segs = nullptr; c->segs_cap = 0; }
   c->d_leaf_start = nullptr; c->d_params = nullptr; c->d_maxerr = nullptr; c->d_run = nullptr;
   c->d_err = nullptr; c->d_count = nullptr; c->d_rows = nullptr; c->d_tilemin = nullptr;
   c->cap_leaves = 0; c->cap_ppl = 0;
@@ -430,10 +368,7 @@ void rmi_hip_destroy(rmi_hip_ctx* c) {
       std::fprintf(stderr, "k_leaf_regs cycles (sum over waves and trainings): fit %llu, epilogue+tail %llu, hand-over %llu, error pass %llu, finalize %llu; (unused %llu) hand-over requests %llu, (unused %llu), finalize stores %llu, finalize up to the shuffles' end %llu; RG_PROF 2, inside the fit: panel requests %llu, stash %llu, arithmetic %llu, constants + landed %llu, wait for the panel %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[5], h[7], h[8], h[9], h[11]);
     (void)hipFree(c->d_regprof);
   }
-  if (c->d_slow_list) (void)hipFree(c->d_slow_list);
-  if (c->d_tile_slow) (void)hipFree(c->d_tile_slow);
-  if (c->d_bnext) (void)hipFree(c->d_bnext);
-  if (c->d_giant) (void)hipFree(c->d_giant);
+  release(c->d_slow_list, c->slow_cap); release(c->d_tile_slow, c->tile_slow_cap); release(c->d_bnext, c->bnext_cap); release(c->d_giant, c->giant_cap);
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_sentinel) (void)hipHostFree(c->h_sentinel);
   for (int b = 0; b < 2; b++) { if (c->h_stage[b]) (void)hipHostFree(c->h_stage[b]); if (c->ev_stage[b]) (void)hipEventDestroy(c->ev_stage[b]); }
@@ -457,7 +392,7 @@ int rmi_hip_set_fit_mode(rmi_hip_ctx* c, int mode, double guard_k) {
   if (!c || mode < 0 || mode > 2) return RMI_ERR_BAD_ARG;
   c->fit_mode = mode;
   if (guard_k > 0.0) c->guard_k = guard_k;
-  c->hint_epoch = 0;                               // (what the last mode learned about the key set does not carry over)
+  c->mem.hint_epoch = 0;                           // (what the last mode learned about the key set does not carry over)
   return RMI_OK;
 }
 
@@ -549,8 +484,7 @@ int rmi_hip_train_many(rmi_hip_ctx* c, const rmi_hip_train_config* cfgs, uint64_
     const int arc = rmi_hip_attach_device_keys(v, c->d_keys, c->n, c->dtype);
     if (arc != RMI_OK) return arc;
     // what the caller has set on the context holds for every training of the batch
-    v->fit_mode = c->fit_mode; v->guard_k = c->guard_k; v->profile_level = c->profile_level; v->host_min = c->host_min; v->host_min_set = c->host_min_set;
-    v->long_min = c->long_min; v->pipeline = c->pipeline; v->regs = c->regs; v->regs_forced = c->regs_forced; v->regs_u32 = c->regs_u32; v->opt_tail = c->opt_tail;
+    v->knobs = c->knobs; v->fit_mode = c->fit_mode; v->guard_k = c->guard_k; v->profile_level = c->profile_level;
   }
   std::atomic<uint64_t> next{0};
   std::vector<int> lrc(count, RMI_OK);
@@ -742,6 +676,21 @@ int rmi_hip_measure_read_bandwidth_ex(rmi_hip_ctx* c, int iters, int pattern, do
 
 }  // extern "C"
 
+// The bucketing scan: first[j] = index of the first key whose target is j, for the targets the keys reach ...
+template <int ROOT, typename K>
+static void launch_bounds(hipStream_t s, const K* keys, uint64_t n, const Span& sp, const RootP& rp, unsigned long long* first, DevState* st) {
+  constexpr uint64_t V = 16 / sizeof(K);
+  const uint64_t blocks = ((n + V - 1) / V + 256 * BV_UNROLL - 1) / (256 * BV_UNROLL);
+  hipLaunchKernelGGL((k_bounds_vec<ROOT, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, rp, first, st);
+}
+// ... and the fill of the `count` entries: a target no key reaches starts where the next one does (tmin: the tiles' minima)
+static void launch_fill(hipStream_t s, unsigned long long* first, uint64_t count, unsigned long long* tmin) {
+  const uint64_t ntiles = (count + FILL_TILE - 1) / FILL_TILE;
+  hipLaunchKernelGGL(k_fill_tilemin, dim3((unsigned)ntiles), dim3(256), 0, s, first, count, tmin);
+  hipLaunchKernelGGL(k_fill_scan_tiles, dim3(1), dim3(1024), 0, s, tmin, ntiles);
+  hipLaunchKernelGGL(k_fill_apply, dim3((unsigned)ntiles), dim3(256), 0, s, first, count, tmin);
+}
+
 // Bucketing scan of the resident keys with a radix-family root over `bins` bins:
 // d_first[j] = index of the first key whose bin is >= j (j in [0, bins]; d_first[bins] = n), on
 // the stream of the context.  d_first: bins + 1 entries; d_tmin: bin_starts_tiles(bins) + 1.
@@ -749,18 +698,13 @@ static uint64_t bin_starts_tiles(uint64_t bins) { return (bins + 1 + FILL_TILE -
 template <typename K>
 static void launch_bin_starts(rmi_hip_ctx* c, const RootP& rp, uint64_t bins, unsigned long long* d_first, unsigned long long* d_tmin) {
   hipStream_t s = c->stream;
-  const uint64_t ntiles = bin_starts_tiles(bins);
   Span sp; sp.it_lo = 0; sp.it_hi = c->n; sp.rd_lo = 0; sp.rd_hi = c->n; sp.n = c->n; sp.leaf_lo = 0; sp.leaf_hi = bins;
   DevState init; std::memset(&init, 0, sizeof init);
   init.split_idx = c->n; init.last_target = ~0ull;
   (void)hipMemcpyAsync(c->d_state, &init, sizeof init, hipMemcpyHostToDevice, s);
   hipLaunchKernelGGL(k_table_init, dim3(1024), dim3(256), 0, s, d_first, bins);
-  constexpr uint64_t V = 16 / sizeof(K);
-  const uint64_t blocks = ((c->n + V - 1) / V + 256 * BV_UNROLL - 1) / (256 * BV_UNROLL);
-  hipLaunchKernelGGL((k_bounds_vec<K_RADIX, K>), dim3((unsigned)blocks), dim3(256), 0, s, (const K*)c->d_keys, sp, rp, d_first, c->d_state);
-  hipLaunchKernelGGL(k_fill_tilemin, dim3((unsigned)ntiles), dim3(256), 0, s, d_first, bins + 1, d_tmin);
-  hipLaunchKernelGGL(k_fill_scan_tiles, dim3(1), dim3(1024), 0, s, d_tmin, ntiles);
-  hipLaunchKernelGGL(k_fill_apply, dim3((unsigned)ntiles), dim3(256), 0, s, d_first, bins + 1, d_tmin);
+  launch_bounds<K_RADIX, K>(s, (const K*)c->d_keys, c->n, sp, rp, d_first, c->d_state);
+  launch_fill(s, d_first, bins + 1, d_tmin);
 }
 
 // Radix-table root fitted where the keys are: bucketing scan over the table's slots, fill, scale.
@@ -781,12 +725,7 @@ static int fit_radix_table_device(rmi_hip_ctx* c, int kind, uint64_t num_leaves,
   unsigned long long* d_tmin = nullptr;
   HIPCHK(c, hipMalloc(&d_first, (slots + 1) * 8));
   if (hipMalloc(&d_tmin, (bin_starts_tiles(slots) + 1) * 8) != hipSuccess) { (void)hipFree(d_first); return RMI_ERR_HIP; }
-  if (c->d_table_cap < slots) {
-    if (c->d_table) (void)hipFree(c->d_table);
-    c->d_table = nullptr; c->d_table_cap = 0;
-    if (hipMalloc(&c->d_table, slots * 4) != hipSuccess) { (void)hipFree(d_first); (void)hipFree(d_tmin); return RMI_ERR_HIP; }
-    c->d_table_cap = slots;
-  }
+  if (const int grc = grow(c, c->d_table, c->d_table_cap, slots, 4)) { (void)hipFree(d_first); (void)hipFree(d_tmin); return grc; }
   int rc = RMI_OK;
   if (prefix == 64) {
     // every key is the same value x: the masked shifts of radix.rs:98-99 leave slot = x
@@ -1044,12 +983,7 @@ int rmi_hip_fit_root(rmi_hip_ctx* c, int root_kind, uint64_t num_leaves, const v
 int rmi_hip_set_root_table(rmi_hip_ctx* c, const uint32_t* table, uint64_t entries) {
   if (!c || !table || entries == 0 || (entries & (entries - 1))) return RMI_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->d_table_cap < entries) {
-    if (c->d_table) (void)hipFree(c->d_table);
-    c->d_table = nullptr; c->d_table_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_table, entries * 4));
-    c->d_table_cap = entries;
-  }
+  if (const int grc = grow(c, c->d_table, c->d_table_cap, entries, 4)) return grc;
   HIPCHK(c, hipStreamSynchronize(c->stream));                  // a train call may still be reading the old table
   if (table != c->h_table.data()) c->h_table.assign(table, table + entries);
   HIPCHK(c, hipMemcpy(c->d_table, c->h_table.data(), entries * 4, hipMemcpyHostToDevice));
@@ -1172,524 +1106,329 @@ static void host_cubes(double* v, uint64_t n) {
   for (auto& x : th) x.join();
 }
 
+// ---- the launchers of a training: launch_pipeline plans the route (rmi_route.h) and hands it to one of them ----
+
+// An event between two kernel groups costs ~5.5 us of idle device time (measured in the kernel trace): profile level 0 records
+// the start and the end of the call only, level 1 also brackets the first, dominant kernel, level 2 every kernel group.
+struct Marks {
+  rmi_hip_ctx* c; hipStream_t s; int pl; int evi;
+  hipError_t begin() { return pl >= 1 ? hipEventRecord(c->ev[0], s) : hipSuccess; }   // (the bracket of the dominant kernel starts here)
+  void operator()() { if (pl >= 2 || (pl == 1 && evi == 0)) (void)hipEventRecord(c->ev[1 + evi], s); evi++; }
+};
+
+// One launch's index space and outputs (global indices, see Span: ptr[j] is leaf j's element, keys[i] key i's)
+template <typename K>
+struct Launch {
+  hipStream_t s; Span sp;
+  uint64_t L, L_own, n_it;                      // leaves of the model, of this launch; keys of this launch
+  const K* keys;
+  unsigned long long* a_leaf_start;             // (not offset: k_init and the fill index from the launch's first leaf)
+  unsigned long long *leaf_start, *maxerr, *run, *err, *count;
+  double* params; unsigned char* rows;
+  DevState init; Marks mark;
+};
+
+static SgList flist_of(const rmi_hip_ctx* c) { SgList fl; fl.ids = c->d_flist; fl.cnt = c->d_flist_cnt; fl.cap = c->flist_cap; return fl; }
+static unsigned int lanes_long_min(const rmi_hip_ctx* c) { return c->knobs.long_min < (unsigned int)LN_LONG_MAX ? c->knobs.long_min : (unsigned int)LN_LONG_MAX; }
+// (pass A's table covers FS_TMAX counts: its long leaves have at least that many points)
+static unsigned int pass_a_long_min(const rmi_hip_ctx* c) { return c->knobs.long_min < (unsigned int)FS_TMAX ? (unsigned int)FS_TMAX : c->knobs.long_min; }
+// keys per chunk of the streaming passes: `threads` chunks, whole rows, at least fit_min_chunk keys
+static uint64_t pass_chunk(const rmi_hip_ctx* c, uint64_t n_it, uint64_t threads) {
+  const uint64_t C = ((n_it + threads - 1) / threads + FS_ROW - 1) / FS_ROW * FS_ROW;
+  return C < (uint64_t)c->knobs.fit_min_chunk ? (uint64_t)c->knobs.fit_min_chunk : C;
+}
+
+// the hand-over lists of the leaf kernels: SG_REGIONS regions of leaf ids, and the stretches of the long listed leaves (k_list -> k_list_tail)
+static int ensure_lists(rmi_hip_ctx* c, uint64_t n_it, uint64_t L_own) {
+  const uint64_t rcap = (L_own + SG_REGIONS - 1) / SG_REGIONS + 8;      // a region holds every leaf with its residue, and the odd re-listed one
+  if (const int grc = grow(c, c->d_flist, c->flist_cap, rcap, 4ull * SG_REGIONS)) return grc;
+  return grow(c, c->d_segs, c->segs_cap, n_it / SG_SEG + L_own + 16, 8);
+}
+
+// giant leaves go to host cores behind the device pipeline (giant_epilogue, which works on the pointers kept in c->lp)
+template <typename K>
+static int arm_giants(rmi_hip_ctx* c, const Launch<K>& a) {
+  if (const int grc = grow(c, c->d_giant, c->giant_cap, a.n_it / c->knobs.host_min + 64, sizeof(GiantLeaf))) return grc;
+  c->giant_armed = true;
+  if (!c->h_giant) HIPCHK(c, hipHostMalloc((void**)&c->h_giant, 8 + rmi_hip_ctx::GIANT_EARLY_MAX * sizeof(GiantLeaf), hipHostMallocDefault));
+  if (!c->ev_giant) HIPCHK(c, hipEventCreateWithFlags(&c->ev_giant, hipEventDisableTiming));
+  c->lp.keys = a.keys; c->lp.sp = a.sp; c->lp.L = a.L; c->lp.leaf_start = a.leaf_start; c->lp.params = a.params; c->lp.maxerr = a.maxerr; c->lp.run = a.run;
+  c->lp.err = a.err; c->lp.count = a.count; c->lp.rows = a.rows; c->lp.waves = (a.L_own + 63) / 64;
+  return RMI_OK;
+}
+// ... their list out early (k_giant_scan, a copy into pinned memory, an event): the host walks those chains while k_list fits the other
+// listed leaves (giant_early_fit)
+template <typename K>
+static hipError_t launch_giant_list(rmi_hip_ctx* c, const Launch<K>& a, const SgList& fl) {
+  const uint64_t hgn = c->giant_cap < rmi_hip_ctx::GIANT_EARLY_MAX ? c->giant_cap : rmi_hip_ctx::GIANT_EARLY_MAX;
+  hipLaunchKernelGGL((k_giant_scan<K>), dim3(SG_REGIONS), dim3(64), 0, a.s, a.keys, a.sp, a.leaf_start, c->d_state, fl, c->d_giant, (unsigned long long)c->knobs.host_min);
+  const hipError_t e1 = hipMemcpyAsync(c->h_giant, &c->d_state->giant_count, 8, hipMemcpyDeviceToHost, a.s);
+  const hipError_t e2 = hipMemcpyAsync(c->h_giant + 1, c->d_giant, hgn * sizeof(GiantLeaf), hipMemcpyDeviceToHost, a.s);
+  const hipError_t e3 = hipEventRecord(c->ev_giant, a.s);
+  return e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3;
+}
+
+// sharded training, direct exchange: the leaf kernel stores the rows it finishes to every peer's table too (train_sharded_direct set them);
+// listed leaves follow with the whole slot in the second exchange of the `pending` protocol -- so only with the result published early
+static PeerRows peer_rows(rmi_hip_ctx* c, const rmi_route::Route& r) {
+  PeerRows peers; std::memset(&peers, 0, sizeof peers);
+  c->rows_pushed = r.peers;
+  if (r.peers) peers.n = c->peer_fuse_n;
+  for (int p = 0; p < peers.n; p++) peers.tab[p] = c->peer_fuse_tab[p];
+  return peers;
+}
+
+// pass B, the error pass of the unfused routes
 template <int ROOT, int LEAF, typename K>
-static int launch_pipeline(rmi_hip_ctx* c, const RootP& rp, uint64_t L) {
-  hipStream_t s = c->stream;
-  constexpr int PPL = (LEAF == K_CUBIC) ? 4 : 2;
-  constexpr int ROWB = PPL * 8 + 8;
-  // An event between two kernels costs ~5.5 us of idle device time (measured in the kernel trace):
-  // level 0 records the start and the end of the call only, level 1 also brackets the first,
-  // dominant kernel, level 2 every kernel group.
-  const int pl = c->profile_level;
-  int evi = 0;
-  auto mark = [&]() { if (pl >= 2 || (pl == 1 && evi == 0)) (void)hipEventRecord(c->ev[1 + evi], s); evi++; };
+static void launch_err_range(rmi_hip_ctx* c, const RootP& rp, const Launch<K>& a) {
+  const uint64_t C = pass_chunk(c, a.n_it, c->err_threads), waves = ((a.n_it + C - 1) / C + 63) / 64;
+  hipLaunchKernelGGL((k_err_range<ROOT, LEAF, K>), dim3((unsigned)waves), dim3(64), 0, a.s, a.keys, a.sp, rp, C, a.leaf_start, a.params, a.maxerr, a.run);
+}
 
-  // ---- index space of this launch (global indices; see Span) ----
-  Span sp;
-  if (c->have_shard) sp = c->shard;
-  else { sp.it_lo = 0; sp.it_hi = c->n; sp.rd_lo = 0; sp.rd_hi = c->n; sp.n = c->n; sp.leaf_lo = 0; sp.leaf_hi = L; }
-  const uint64_t n_it = sp.it_hi - sp.it_lo;            // keys this launch works on
-  const uint64_t L_own = sp.leaf_hi - sp.leaf_lo;
-  // pointers pre-offset so that ptr[global index] is the right element
-  // (streamed training: buffers of the whole key set / all leaves, indexed globally)
-  const uint64_t kb = c->stream_mode ? sp.rd_lo : 0, lb = c->stream_mode ? sp.leaf_lo : 0;
-  const K* keys = (const K*)c->d_keys + kb - sp.rd_lo;
-  unsigned long long* const a_leaf_start = c->d_leaf_start + lb;
-  unsigned long long* const a_maxerr = c->d_maxerr + lb;
-  unsigned long long* const a_run = c->d_run + lb;
-  unsigned long long* leaf_start = a_leaf_start - sp.leaf_lo;
-  double* params = c->d_params + lb * PPL - sp.leaf_lo * PPL;
-  unsigned long long* maxerr = a_maxerr - sp.leaf_lo;
-  unsigned long long* run = a_run - sp.leaf_lo;
-  unsigned long long* err = c->d_err + lb - sp.leaf_lo;
-  unsigned long long* count = c->d_count + lb - sp.leaf_lo;
-  unsigned char* rows_base = c->d_rows_ext ? (unsigned char*)c->d_rows_ext : c->d_rows;
-  c->last_rows = rows_base;
-  unsigned char* rows = rows_base + lb * ROWB - sp.leaf_lo * ROWB;
+// leaf ends + aggregates of the unfused routes (bn / bp: the one-pass modes' end keys of every leaf).  The last kernel also copies the
+// device state into the pinned host copy: a separate 100-byte copy command would cost ~15 us of the call.
+template <int LEAF, typename K>
+static void launch_finalize(rmi_hip_ctx* c, const Launch<K>& a, const K* bn, const K* bp) {
+  const uint64_t blocks = (a.L_own + 255) / 256;
+  hipLaunchKernelGGL((k_finalize<LEAF, K>), dim3((unsigned)blocks), dim3(256), 0, a.s, a.keys, a.sp, a.L, a.leaf_start, c->d_state,
+                     a.params, a.maxerr, a.run, a.err, a.count, a.rows, c->d_partials, bn, bp);
+  hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, a.s, c->d_partials, (int)blocks, c->d_state, c->h_state_dev + (c->stream_mode ? c->stream_slot : 0));
+}
 
-  // --- init ---
-  // long-leaf list: a long leaf has at least long_min points, so n/long_min entries always suffice
-  const unsigned int long_min_a = c->long_min < (unsigned int)FS_TMAX ? (unsigned int)FS_TMAX : c->long_min;   // pass A's table covers FS_TMAX counts
-  uint64_t need_long = n_it / long_min_a + 1024;
-  if (c->fit_mode != 0 && need_long < L_own + 1024) need_long = L_own + 1024;      // one-pass mode: every listed leaf goes through k_fit_long
-  if (c->long_cap < need_long) {
-    if (c->d_long) (void)hipFree(c->d_long);
-    c->d_long = nullptr; c->long_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_long, need_long * 8));
-    c->long_cap = need_long;
-  }
-  DevState init; std::memset(&init, 0, sizeof init);
-  init.long_cap = c->long_cap;
-  init.flag_cap = (uint64_t)L_own + 64;
-  init.seg_cap = n_it / SG_SEG + L_own + 16;
-  init.giant_cap = c->host_min > 0 ? n_it / c->host_min + 64 : 0;
-  init.split_idx = (c->have_shard && c->shard_split_idx != ~0ull) ? c->shard_split_idx : sp.n;
-  init.split_target = (c->have_shard && c->shard_split_idx != ~0ull) ? c->shard_split_target : 0;
-  init.last_target = ~0ull;
-  c->giant_armed = false;
-  if (!c->d_flist_cnt) HIPCHK(c, hipMalloc(&c->d_flist_cnt, (2 * SG_REGIONS + 8) * 8));  // (the one-pass mode's list + merge counters: zeroed by k_init)
-  // pipeline 1 launches one thread per key: a grid dimension holds fewer than 2^32 threads
-  const bool stream_fit = (LEAF == K_LINEAR) && !c->robust_leaf;
-  // one pass from sufficient statistics: leaves of at least a few dozen keys on average (the rows of a tile hold
-  // 16 keys; shorter leaves are cheap chains for the exact kernels anyway), indices below 2^32
-  bool hinted = false;
-  if (c->hint_epoch == c->keys_epoch && c->hint_mode == c->fit_mode)
-    for (int h = 0; h < c->hint_n && h < 8; h++) hinted = hinted || c->hint_L[h] == L_own;
-  // linear_spline leaves (the line through a container's two end points) need no sums and no guard: the one-pass kernel
-  // reproduces them bit for bit, so it serves EVERY fit mode (RMI_HIP_SPLINE_ONEPASS=0: the per-pass kernels)
-  // ... and, in front of it, the leaf-lane kernel (two end points per leaf, then its error pass with duplicates handled natively)
-  // pipeline 5 (rmi_scan.hip.h): linear_spline leaves in ONE key-parallel pass, the bucketing scan included -- every root, every key type,
-  // any number of keys (an empty shard as well); 32-bit indices
-  const bool scan5 = c->pipeline >= 3 && (LEAF == K_LINEAR_SPLINE) && sp.n < (1ull << 32) - (1ull << 16);
-  c->last_scan = scan5;
-  const bool spline_l = scan5;                             // (round 6: k_leaf_lanes<.., K_LINEAR_SPLINE>, the second route for these leaves, is gone)
-  // (round 5: the one-pass kernel's linear_spline variant is gone -- k_spline_scan serves them, and where it does not (RMI_HIP_SCAN=0 with
-  //  RMI_HIP_SPLINE_LANES=0, 2^32 keys and more, RMI_HIP_PIPELINE <= 2) the per-pass kernels do; the variant missed the borrowed point of
-  //  a leaf behind an emptied split leaf, Q4)
-  const bool spline1 = false;
-  const bool sigma = ((stream_fit && c->fit_mode != 0) || spline1) && !hinted && sp.n < (1ull << 32) - (1ull << 16) &&
-                     n_it >= (uint64_t)c->sigma_min_leaf * L_own && n_it >= 4096;
-  c->last_sigma = sigma;
-  c->last_spline = sigma && LEAF == K_LINEAR_SPLINE;
-  // exact linear leaves, pipeline 3: the leaf-lane kernels (rmi_lanes.hip.h)
-  const bool lanes = (c->pipeline >= 3 && stream_fit && !sigma && n_it >= 1024) || spline_l;   // (tiny key sets: the streaming passes)
-  c->last_lanes = lanes;
-  // the fused error pass of k_leaf_lanes needs 32-bit indices; with it and the search, k_init has no array to prepare
-  const bool lanes_fused_plan = lanes && c->lanes_fuse && sp.n < (1ull << 32) - (1ull << 16);
-  bool lanes_search_plan = false;
-  if constexpr (ROOT == K_LINEAR) lanes_search_plan = lanes && c->lanes_search && rp.p1 >= 0.0 && std::isfinite(rp.p0) && std::isfinite(rp.p1);
-  // cubic roots: not monotone by arithmetic, but the search may assume it when k_leaf_lanes verifies every key's target
-  // during its (fused) error pass -- no bucketing scan, no fill
-  if constexpr (ROOT == K_CUBIC) lanes_search_plan = lanes && c->lanes_search && lanes_fused_plan && LEAF == K_LINEAR && std::isfinite(rp.p0) && std::isfinite(rp.p1) && std::isfinite(rp.p2) && std::isfinite(rp.p3);
-  bool scan_mono = false;                                  // pipeline 5: the root is monotone by arithmetic (its short form of a tile relies on it)
-  if constexpr (ROOT == K_LINEAR) scan_mono = scan5 && rp.p1 >= 0.0 && std::isfinite(rp.p0) && std::isfinite(rp.p1);
-  if constexpr (ROOT == K_RADIX) {
-    // (key << prefix) >> (64 - bits) is monotone in the key exactly when no key loses a distinguishing bit to the
-    // shift: all resident keys share their top `prefix` bits.  First and last key of the sorted set decide; fetched once per key set.
-    if ((lanes && c->lanes_search) || scan5) {
-      if (c->edge_epoch != c->keys_epoch) {
-        K k0{}, k1{};
-        HIPCHK(c, hipMemcpy(&k0, c->d_keys, sizeof(K), hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&k1, (const K*)c->d_keys + (c->n - 1), sizeof(K), hipMemcpyDeviceToHost));
-        c->edge_first = rmi_host::as_uint(k0); c->edge_last = rmi_host::as_uint(k1); c->edge_epoch = c->keys_epoch;
-      }
-      const unsigned pfx = rp.prefix & 63u;
-      lanes_search_plan = pfx == 0u || ((c->edge_first ^ c->edge_last) >> (64u - pfx)) == 0ull;
-      scan_mono = scan5 && lanes_search_plan;
+// The leaves the leaf kernel handed over (containers too long for the lockstep walk): one wave each, fit + error pass; the listed leaves'
+// share of the finalize, the aggregates, the result record.  With the result published early (Route::optimistic) k_lane_reduce publishes
+// it right behind the leaf kernel and the list kernels wait in c->tail_fn for the host's synchronisation (run only if a leaf was handed over).
+// (The deferred kernels read the context's buffers when they are launched: nothing re-allocates them before the training ends.)
+template <int ROOT, int LEAF, typename K>
+static void launch_tail(rmi_hip_ctx* c, const rmi_route::Route& r, const RootP& rp, Launch<K>& a, const SgList& fl, uint64_t nrec) {
+  SgParams sgp; std::memset(&sgp, 0, sizeof sgp);
+  sgp.flist = fl; sgp.segs = c->d_segs; sgp.mode = 0; sgp.guard_k = c->guard_k;
+  c->last_sg = sgp;
+  StatsPartial* const part = c->d_partials;
+  DevState* const hcopy = c->h_state_dev + (c->stream_mode ? c->stream_slot : 0);
+  GiantLeaf* const dgiant = r.giants ? c->d_giant : (GiantLeaf*)nullptr;
+  const unsigned long long hmin = r.giants ? (unsigned long long)c->knobs.host_min : ~0ull;
+  auto tail = [=](auto&& mk) {
+    if constexpr (ROOT == K_CUBIC && LEAF == K_LINEAR) {
+      if (r.verify) hipLaunchKernelGGL((k_verify_listed<K_CUBIC, K>), dim3(1024), dim3(256), 0, a.s, a.keys, a.sp, rp, a.leaf_start, c->d_state, fl);
     }
-  }
-  if (scan5) lanes_search_plan = false;                    // (the scan finds the leaf starts itself)
-  const bool init_arrays = scan5 ? false : !(lanes_fused_plan && lanes_search_plan);
-  if ((!c->stream_mode || c->stream_slot == 0) && pl >= 0) HIPCHK(c, hipEventRecord(c->ev[8], s));   // start of the device work of this call
-  // (the leaf-lane pipeline with its search and its fused error pass: the launch of k_leaf_samples carries the init)
-  const bool init_folded = !scan5 && !init_arrays && (LEAF == K_LINEAR || LEAF == K_LINEAR_SPLINE);
-  if (!init_folded) {
-    const uint64_t ib = init_arrays ? (L_own + 1 + 255) / 256 : 1;
-    hipLaunchKernelGGL(k_init, dim3((unsigned)(ib < 2048 ? ib : 2048)), dim3(256), 0, s, a_leaf_start, a_maxerr, a_run,
-                       L_own, (unsigned long long)sp.it_hi, c->d_state, init, c->d_flist_cnt, 2 * SG_REGIONS + 8, init_arrays, scan5 ? c->d_tickets : (unsigned int*)nullptr);
-  }
-  c->tail_armed = false; c->tail_fn = nullptr; c->regs_listed_fn = nullptr; c->giant_early = false; c->giant_fitted = false;
-  c->last_lean = false; c->lean_derived = false;
-
-  auto ensure_lists = [&]() -> int {
-    const uint64_t rcap = (L_own + SG_REGIONS - 1) / SG_REGIONS + 8;      // a region holds every leaf with its residue, and the odd re-listed one
-    if (c->flist_cap < rcap) {
-      if (c->d_flist) (void)hipFree(c->d_flist);
-      c->d_flist = nullptr; c->flist_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_flist, rcap * SG_REGIONS * 4));
-      c->flist_cap = rcap;
-    }
-    const uint64_t scap = n_it / SG_SEG + L_own + 16;                     // stretches of the long listed leaves (k_list -> k_list_tail)
-    if (c->segs_cap < scap) {
-      if (c->d_segs) (void)hipFree(c->d_segs);
-      c->d_segs = nullptr; c->segs_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_segs, scap * 8));
-      c->segs_cap = scap;
-    }
-    return RMI_OK;
+    // (one wave per listed leaf wherever possible: on skewed keys thousands of leaves are listed and each is a sequential chain)
+    if (r.giants_early) (void)launch_giant_list(c, a, fl);
+    hipLaunchKernelGGL((k_list<K, LEAF>), dim3(128 * SG_REGIONS), dim3(64), 0, a.s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, fl, sgp, a.maxerr, a.run,
+                       dgiant, hmin, !r.giants_early);
+    mk();
+    // (waves' aggregate records: [0, nrec); their slice sums, by k_list_tail: [nrec, nrec + SG_REGIONS); the records of k_finalize_listed behind)
+    hipLaunchKernelGGL((k_list_tail<K>), dim3(2048), dim3(64), 0, a.s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, fl, c->d_segs, a.maxerr, a.run,
+                       r.fused ? (const StatsPartial*)part : (const StatsPartial*)nullptr, (unsigned int)nrec, part + nrec);
+    mk();
+    if (r.fused)
+      hipLaunchKernelGGL((k_finalize_listed<K>), dim3(FL_BLOCKS), dim3(FL_THREADS), 0, a.s, a.keys, a.sp, a.L, a.leaf_start, c->d_state, a.params, a.maxerr, a.run, a.err,
+                         a.count, a.rows, fl, part + nrec, (unsigned int)SG_REGIONS, part + nrec + SG_REGIONS, c->d_flist_cnt + 2 * SG_REGIONS, c->d_state, hcopy,
+                         (const GiantLeaf*)nullptr, hmin);
   };
-  // giant leaves go to the host when this call ends with its own synchronisation (not inside a streamed or a sharded training)
-  auto arm_giants = [&]() -> int {
-    const uint64_t gcap = n_it / c->host_min + 64;
-    if (c->giant_cap < gcap) {
-      if (c->d_giant) (void)hipFree(c->d_giant);
-      c->d_giant = nullptr; c->giant_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_giant, gcap * sizeof(GiantLeaf)));
-      c->giant_cap = gcap;
-    }
-    c->giant_armed = true;
-    if (!c->h_giant) HIPCHK(c, hipHostMalloc((void**)&c->h_giant, 8 + rmi_hip_ctx::GIANT_EARLY_MAX * sizeof(GiantLeaf), hipHostMallocDefault));
-    if (!c->ev_giant) HIPCHK(c, hipEventCreateWithFlags(&c->ev_giant, hipEventDisableTiming));
-    c->lp.keys = keys; c->lp.sp = sp; c->lp.L = L; c->lp.leaf_start = leaf_start; c->lp.params = params; c->lp.maxerr = maxerr; c->lp.run = run;
-    c->lp.err = err; c->lp.count = count; c->lp.rows = rows; c->lp.waves = (L_own + 63) / 64;
-    return RMI_OK;
+  if (r.optimistic) {
+    const unsigned int nsl = (unsigned int)((nrec + LF_SLICE - 1) / LF_SLICE);
+    hipLaunchKernelGGL(k_lane_reduce, dim3(nsl), dim3(LF_SLICE), 0, a.s, (const StatsPartial*)part, (unsigned int)nrec, part + nrec + SG_REGIONS + 2 * FL_BLOCKS + 1,
+                       c->d_tickets, fl, c->d_state, hcopy);
+    a.mark(); a.mark();
+    c->tail_armed = true;
+    c->giant_early = r.giants_early;
+    c->tail_fn = [tail]() -> int { tail([]() {}); return RMI_OK; };
+  } else tail(a.mark);
+}
+
+// Pipeline 4: k_leaf_regs (one read of the keys), the groups it listed (k_leaf_lanes_listed), the leaf ends (k_regs_finalize).
+template <typename K>
+static int launch_regs(rmi_hip_ctx* c, const rmi_route::Route& r, const RootP& rp, Launch<K>& a, const SgList& fl, const PeerRows& peers) {
+  const uint64_t wb = (a.L_own + 63) / 64;
+  if (const int grc = grow(c, c->d_slow_list, c->slow_cap, wb, 4)) return grc;
+  if (const int grc = grow(c, c->d_tile_slow, c->tile_slow_cap, wb, 1)) return grc;
+  if (const int grc = grow(c, c->d_bnext, c->bnext_cap, wb, 64 * 16)) return grc;   // (the keys on either side of every leaf: 2 x 8 bytes)
+  HIPCHK(c, hipGetLastError());
+  const unsigned int lmin = lanes_long_min(c);
+  StatsPartial* const part = c->d_partials;
+  K* const bnext = (K*)c->d_bnext, * const bprev = bnext + wb * 64;
+  // (the kernel's debugging switches stay off: no group listed by force, the groups dealt by wave number rather than from a counter)
+  auto regs = [&](auto variant) {
+    hipLaunchKernelGGL((k_leaf_regs<K, decltype(variant)::value>), dim3(r.regs_grid), dim3(64), 0, a.s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, c->d_lntab,
+                       c->d_regtab, fl, lmin, a.maxerr, a.run, a.L, a.err, a.count, a.rows, part, rp, peers, (unsigned int)wb, c->knobs.regs_backoff ? 2u : 0u,
+                       c->d_slow_list, c->d_tickets + 1, c->d_regprof, bnext, bprev, c->d_tile_slow, (unsigned int*)nullptr);
   };
-  c->refinalize_fn = nullptr;
-  bool lanes_fused = false;
-  if (lanes) {
-    if constexpr (LEAF == K_LINEAR || LEAF == K_LINEAR_SPLINE) {
-      { const int lrc = ensure_lists(); if (lrc != RMI_OK) return lrc; }
-      // --- leaf boundaries: lower bounds by search where the root is monotone by arithmetic, else the bucketing scan + fill ---
-      bool searched = false;
-      const uint64_t wb = (L_own + 63) / 64;
-      uint64_t nrec = wb;                                               // aggregate records the fitting kernel leaves (one per wave)
-      // the result published by k_lane_reduce right behind k_leaf_lanes; the list kernels behind the synchronisation, if a leaf was handed over
-      const bool optimistic = lanes_fused_plan && c->opt_tail && !c->stream_mode;
-      if constexpr (ROOT == K_LINEAR || ROOT == K_RADIX || ROOT == K_CUBIC) {
-        if (lanes_search_plan) {
-          const uint64_t sb = (L_own + (uint64_t)LS_BLOCK * LS_ILP - 1) / ((uint64_t)LS_BLOCK * LS_ILP);
-          double* smp = c->d_lntab + 3 * LN_TMAX;                       // 2 (LS_SAMPLES + 1) doubles behind the step tables
-          LaneInit li; std::memset(&li, 0, sizeof li);
-          if (init_folded) {
-            li.st = c->d_state; li.init = init; li.leaf_start = a_leaf_start; li.L_own = L_own; li.sentinel = (unsigned long long)sp.it_hi;
-            li.list_cnt = c->d_flist_cnt; li.n_list_cnt = 2 * SG_REGIONS + 8; li.tickets = c->d_tickets; li.n_tickets = 3;
-          }
-          hipLaunchKernelGGL((k_leaf_samples<ROOT, K>), dim3((LS_SAMPLES + 256) / 256), dim3(256), 0, s, keys, sp, rp, smp, li);
-          hipLaunchKernelGGL((k_leaf_search<ROOT, K, LS_ILP>), dim3((unsigned)sb), dim3(LS_BLOCK), 0, s, keys, sp, rp, leaf_start, c->d_state, (const double*)smp);
-          searched = true;
-        }
+  if (r.regs == 0) regs(std::integral_constant<int, 0>{});
+  else if (r.regs == 1) regs(std::integral_constant<int, 1>{});
+  else if constexpr (sizeof(K) == 4) regs(std::integral_constant<int, 2>{});
+  a.mark();                                                            // (slot 0: k_leaf_regs alone; slot 1: the listed groups + k_regs_finalize)
+  // The groups k_leaf_regs listed.  As a rule there are none: with the result published early (k_lane_reduce) and the host
+  // synchronising itself, the kernel is launched only when the record says a group was listed (DevState::regs_listed) --
+  // an empty launch cost 4.6 us and a gap in every step; in-stream otherwise (a sharded or streamed training).
+  auto listed = [=](unsigned int grid_l) {
+    hipLaunchKernelGGL((k_leaf_lanes_listed<K>), dim3(grid_l), dim3(64), 0, a.s, c->d_slow_list, c->d_tickets + 1, a.keys, a.sp, a.leaf_start, c->d_state, a.params,
+                       c->d_lntab, fl, lmin, a.maxerr, a.run, a.L, a.err, a.count, a.rows, part, rp, peers);
+  };
+  if (r.listed_late) {
+    const unsigned int wb_l = (unsigned int)wb;
+    c->regs_listed_fn = [=](unsigned int groups) -> int {                 // (as many waves as groups: a duplicate-heavy key set lists them all)
+      listed(groups < wb_l ? (groups > 0u ? groups : 1u) : wb_l);
+      hipLaunchKernelGGL(k_lane_reduce, dim3((wb_l + LF_SLICE - 1) / LF_SLICE), dim3(LF_SLICE), 0, a.s, (const StatsPartial*)part, wb_l,
+                         part + wb + SG_REGIONS + 2 * FL_BLOCKS + 1, c->d_tickets, fl, c->d_state, c->h_state_dev);
+      return RMI_OK;
+    };
+  } else listed(wb < 512 ? (unsigned int)wb : 512u);
+  auto finalize = [&](auto vroot, double scale) {
+    hipLaunchKernelGGL((k_regs_finalize<K, decltype(vroot)::value>), dim3((unsigned)((wb * 64 + 255) / 256)), dim3(256), 0, a.s, a.keys, a.sp, a.L, a.leaf_start, c->d_state,
+                       (const unsigned int*)(c->d_tickets + 1), a.params, (const unsigned long long*)a.maxerr, (const K*)bnext, (const K*)bprev,
+                       (const unsigned char*)c->d_tile_slow, (unsigned int)wb, a.err, a.count, a.rows, part, peers, rp, scale, r.listed_late);
+  };
+  if (r.cubic_margin) finalize(std::integral_constant<int, K_CUBIC>{}, c->knobs.cubic_margin_scale);
+  else finalize(std::integral_constant<int, -1>{}, 1.0);
+  HIPCHK(c, hipGetLastError());
+  return RMI_OK;
+}
+
+// Pipelines 3 and 4, exact linear leaves: the leaf boundaries (search, or the bucketing scan + fill), k_leaf_regs (4) or k_leaf_lanes (3; a
+// cubic root's verifies every key's target), the list tail, and where the error pass is not fused (2^32 keys and more) k_err_range + k_finalize.
+template <int ROOT, typename K>
+static int launch_leaf_lanes(rmi_hip_ctx* c, const rmi_route::Route& r, const RootP& rp, Launch<K>& a) {
+  hipStream_t s = a.s;
+  const uint64_t L_own = a.L_own, wb = (L_own + 63) / 64;
+  if (const int lrc = ensure_lists(c, a.n_it, L_own)) return lrc;
+  if constexpr (ROOT == K_LINEAR || ROOT == K_RADIX || ROOT == K_CUBIC) {
+    if (r.search) {
+      const uint64_t sb = (L_own + (uint64_t)LS_BLOCK * LS_ILP - 1) / ((uint64_t)LS_BLOCK * LS_ILP);
+      double* smp = c->d_lntab + 3 * LN_TMAX;                           // 2 (LS_SAMPLES + 1) doubles behind the step tables
+      LaneInit li; std::memset(&li, 0, sizeof li);
+      if (r.init_folded) {
+        li.st = c->d_state; li.init = a.init; li.leaf_start = a.a_leaf_start; li.L_own = L_own; li.sentinel = (unsigned long long)a.sp.it_hi;
+        li.list_cnt = c->d_flist_cnt; li.n_list_cnt = 2 * SG_REGIONS + 8; li.tickets = c->d_tickets; li.n_tickets = 3;
       }
-      if (!(searched && init_folded) && !scan5) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, 12, s));   // (k_lane_reduce's arrival counter, k_leaf_regs' list counter and group counter)
-      if (!searched && !scan5) {
-        constexpr uint64_t V = 16 / sizeof(K);
-        const uint64_t blocks = ((n_it + V - 1) / V + 256 * BV_UNROLL - 1) / (256 * BV_UNROLL);
-        hipLaunchKernelGGL((k_bounds_vec<ROOT, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, rp, leaf_start, c->d_state);
-        const uint64_t count_e = L_own + 1;
-        const uint64_t ntiles = (count_e + FILL_TILE - 1) / FILL_TILE;
-        hipLaunchKernelGGL(k_fill_tilemin, dim3((unsigned)ntiles), dim3(256), 0, s, a_leaf_start, count_e, c->d_tilemin);
-        hipLaunchKernelGGL(k_fill_scan_tiles, dim3(1), dim3(1024), 0, s, c->d_tilemin, ntiles);
-        hipLaunchKernelGGL(k_fill_apply, dim3((unsigned)ntiles), dim3(256), 0, s, a_leaf_start, count_e, c->d_tilemin);
-      }
-      if (pl >= 1) HIPCHK(c, hipEventRecord(c->ev[0], s));              // (the bracket of the dominant kernel starts here)
-      // --- exact fit of 64 leaves per wave in lockstep, and their error pass behind it ---
-      lanes_fused = lanes_fused_plan;
-      SgList fl; fl.ids = c->d_flist; fl.cnt = c->d_flist_cnt; fl.cap = c->flist_cap;
-      // (giant leaves are for the OUTLIERS of a skewed key set: where the average leaf is within a factor of four of the threshold nearly every leaf would go
-      //  to the host -- 400 M u32 keys in 1 024 leaves: 680 ms, the keys over PCIe and 1 024 chains on a few cores, against 14 ms of 1 024 waves side by side)
-      const bool giants_pay = c->host_min > 0 && (c->host_min_set || n_it / (L_own ? L_own : 1) <= c->host_min / 4);
-      const bool giants = LEAF == K_LINEAR && lanes_fused_plan && giants_pay && !c->stream_mode && !c->defer_sync;
-      if (giants) { const int grc = arm_giants(); if (grc != RMI_OK) return grc; }
-      const unsigned int lmin = c->long_min < (unsigned int)LN_LONG_MAX ? c->long_min : (unsigned int)LN_LONG_MAX;
-      StatsPartial* const part = c->d_partials;
-      // sharded training with the direct exchange: the rows of the leaves k_leaf_lanes finishes go to every peer's table from
-      // the kernel itself (train_sharded_direct has set the tables of this epoch); leaves handed to the list kernels follow
-      // with the whole slot in the second exchange of the `pending` protocol
-      PeerRows peers; std::memset(&peers, 0, sizeof peers);
-      c->rows_pushed = false;
-      // (only with the published-early result: with the list kernels in-stream, RMI_HIP_OPT_TAIL=0, `pending` is 0, no second exchange
-      //  follows, and the rows of the listed leaves would never reach the peers -- k_peer_push then carries the whole slot)
-      if (lanes_fused_plan && c->peer_fuse_n > 0 && optimistic) {   // (linear and linear_spline leaves: rows of 24 bytes)
-        peers.n = c->peer_fuse_n;
-        for (int p = 0; p < peers.n; p++) peers.tab[p] = c->peer_fuse_tab[p];
-        c->rows_pushed = true;
-      }
-      // pipeline 4's conditions besides the root's: 8-byte keys, linear leaves, leaves short enough on average that most groups of 64 qualify,
-      // not a key set on which k_leaf_regs listed most groups last time
-      bool regs_plan = false, regs_long = false;
-      if constexpr (LEAF == K_LINEAR) {
-        bool regs_off = false;
-        if (c->regs_off_epoch == c->keys_epoch)
-          for (int h = 0; h < c->regs_off_n && h < 8; h++) regs_off = regs_off || c->regs_off_L[h] == L_own;
-        regs_long = n_it > (uint64_t)c->regs_max_avg * L_own;            // long leaves on average: the LONG variant of the kernel
-        const unsigned int cap = c->regs_long_max_avg > c->regs_max_avg ? c->regs_long_max_avg : c->regs_max_avg;
-        regs_plan = lanes_fused_plan && c->regs && !regs_off && c->pipeline >= 3 && n_it <= (uint64_t)cap * L_own && (sizeof(K) == 8 || c->regs_u32);
-        // Between one and two and a half groups per resident wave (M's shard at 8 GPUs: 2 048 groups on 1 024 waves) k_leaf_regs runs two rounds of a
-        // group each behind its 20 us of start-up, k_leaf_lanes ONE round on twice the waves: measured 0.110 against 0.120 ms at 2 048 groups, equal
-        // at 1 024, 0.186 against 0.177 at 4 096.
-        {
-          const uint64_t resident = 4ull * (uint64_t)c->n_cu;
-          if (!regs_long && !c->regs_forced && c->regs_grid == 0 && wb > resident && 2 * wb <= 5 * resident) regs_plan = false;
-        }
-      }
-      // a cubic root on pipeline 4: increasing over the resident keys' range as an exact polynomial (here), every leaf's end keys clear
-      // their leaf's interval by the rounding bound (k_regs_finalize<K, K_CUBIC>) -- else the per-key verification of k_leaf_lanes
-      bool cubic_margin = false;
-      if constexpr (ROOT == K_CUBIC && LEAF == K_LINEAR) {
-        if (searched && regs_plan && c->cubic_margin) {
-          if (c->edgef_epoch != c->keys_epoch) {
-            K k0{}, k1{};
-            HIPCHK(c, hipMemcpy(&k0, c->d_keys, sizeof(K), hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(&k1, (const K*)c->d_keys + (c->n - 1), sizeof(K), hipMemcpyDeviceToHost));
-            c->edge_first_f = rmi_host::as_float(k0); c->edge_last_f = rmi_host::as_float(k1); c->edgef_epoch = c->keys_epoch;
-          }
-          cubic_margin = cubic_increasing_on(rp, c->edge_first_f, c->edge_last_f);
-        }
-      }
-      bool verify = false;
-      if constexpr (ROOT == K_CUBIC && LEAF == K_LINEAR) {
-        if (searched && !cubic_margin) {                                // (searched implies fused: the verification rides on the error pass)
-          hipLaunchKernelGGL((k_leaf_lanes<K, true, K_LINEAR, K_CUBIC>), dim3((unsigned)wb), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, c->d_lntab, fl, lmin, maxerr, run,
-                             L, err, count, rows, part, rp, peers);
-          verify = true;
-        }
-      }
-      // pipeline 4: one read of the keys (8-byte keys, linear leaves, leaves short enough on average that most groups of 64 qualify)
-      bool regs = false;
-      if constexpr (LEAF == K_LINEAR) {
-        // (a key set on which k_leaf_regs listed most groups -- duplicate-heavy keys: every group meets a duplicate -- is remembered, like
-        //  the one-pass modes' hint: the next trainings of it with that many leaves go straight to k_leaf_lanes, 0.80 against 2.25 ms)
-        regs = !verify && lanes_fused && regs_plan;
-        if (regs) {
-          if (c->slow_cap < wb) {
-            if (c->d_slow_list) (void)hipFree(c->d_slow_list);
-            if (c->d_tile_slow) (void)hipFree(c->d_tile_slow);
-            if (c->d_bnext) (void)hipFree(c->d_bnext);
-            c->d_slow_list = nullptr; c->d_tile_slow = nullptr; c->d_bnext = nullptr; c->slow_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_slow_list, wb * 4));
-            HIPCHK(c, hipMalloc(&c->d_tile_slow, wb));
-            HIPCHK(c, hipMalloc(&c->d_bnext, wb * 64 * 16));                // (the keys on either side of every leaf: 2 x 8 bytes)
-            c->slow_cap = wb;
-          }
-          HIPCHK(c, hipGetLastError());
-          const bool w2 = sizeof(K) == 4 && c->regs_u32 >= 2;           // two waves per SIMD
-          unsigned int grid = c->regs_grid ? c->regs_grid : (w2 ? 8u : 4u) * (unsigned int)c->n_cu;
-          if ((uint64_t)grid > wb) grid = (unsigned int)wb;
-          // (the variant: 0 = leaves that fit the stash and the ring, 1 = LONG, 2 = 4-byte keys at two waves per SIMD)
-          auto launch_regs = [&](auto variant_tag) {
-            constexpr int VARIANT = decltype(variant_tag)::value;
-            hipLaunchKernelGGL((k_leaf_regs<K, VARIANT>), dim3(grid), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, c->d_lntab, c->d_regtab, fl, lmin, maxerr, run,
-                               L, err, count, rows, part, rp, peers, (unsigned int)wb, (c->regs_slow & 1u) | (c->regs_backoff ? 2u : 0u), c->d_slow_list, c->d_tickets + 1, c->d_regprof,
-                               (K*)c->d_bnext, (K*)c->d_bnext + wb * 64, c->d_tile_slow, c->regs_queue ? c->d_tickets + 2 : (unsigned int*)nullptr);
-          };
-          bool launched = false;
-          if constexpr (sizeof(K) == 4) { if (w2) { launch_regs(std::integral_constant<int, 2>{}); launched = true; } }
-          if (!launched) { if (regs_long) launch_regs(std::integral_constant<int, 1>{}); else launch_regs(std::integral_constant<int, 0>{}); }
-          mark();                                                       // (slot 0: k_leaf_regs alone; slot 1: the listed groups + k_regs_finalize)
-          // The groups k_leaf_regs listed.  As a rule there are none: with the result published early (k_lane_reduce) and the host
-          // synchronising itself, the kernel is launched only when the record says a group was listed (DevState::regs_listed) --
-          // an empty launch cost 4.6 us and a gap in every step; in-stream otherwise (a sharded or streamed training).
-          const unsigned int lgrid = wb < 512 ? (unsigned int)wb : 512u;
-          unsigned int* const slow_list = c->d_slow_list;
-          unsigned int* const slow_cnt = c->d_tickets + 1;
-          double* const lntab = c->d_lntab;
-          DevState* const dstate = c->d_state;
-          auto listed = [=](unsigned int grid_l) {
-            hipLaunchKernelGGL((k_leaf_lanes_listed<K>), dim3(grid_l), dim3(64), 0, s, slow_list, slow_cnt, keys, sp, leaf_start, dstate, params, lntab, fl, lmin,
-                               maxerr, run, L, err, count, rows, part, rp, peers);
-          };
-          const bool listed_late = optimistic && !c->defer_sync && peers.n == 0;
-          if (listed_late) {
-            StatsPartial* const slices = part + nrec + SG_REGIONS + 2 * FL_BLOCKS + 1;
-            unsigned int* const tickets = c->d_tickets;
-            DevState* const hcopy_l = c->h_state_dev;
-            const unsigned int nrec_l = (unsigned int)nrec;
-            const unsigned int wb_l = (unsigned int)wb;
-            c->regs_listed_fn = [=](unsigned int groups) -> int {                 // (as many waves as groups: a duplicate-heavy key set lists them all)
-              listed(groups < wb_l ? (groups > 0u ? groups : 1u) : wb_l);
-              hipLaunchKernelGGL(k_lane_reduce, dim3((nrec_l + LF_SLICE - 1) / LF_SLICE), dim3(LF_SLICE), 0, s, (const StatsPartial*)part, nrec_l, slices, tickets, fl, dstate, hcopy_l);
-              return RMI_OK;
-            };
-          } else listed(lgrid);
-          if (cubic_margin)
-            hipLaunchKernelGGL((k_regs_finalize<K, K_CUBIC>), dim3((unsigned)((wb * 64 + 255) / 256)), dim3(256), 0, s, keys, sp, L, leaf_start, c->d_state, (const unsigned int*)(c->d_tickets + 1), params,
-                               (const unsigned long long*)maxerr, (const K*)c->d_bnext, (const K*)c->d_bnext + wb * 64, (const unsigned char*)c->d_tile_slow, (unsigned int)wb,
-                               err, count, rows, part, peers, rp, c->cubic_margin_scale, listed_late);
-          else
-            hipLaunchKernelGGL((k_regs_finalize<K>), dim3((unsigned)((wb * 64 + 255) / 256)), dim3(256), 0, s, keys, sp, L, leaf_start, c->d_state, (const unsigned int*)(c->d_tickets + 1), params,
-                               (const unsigned long long*)maxerr, (const K*)c->d_bnext, (const K*)c->d_bnext + wb * 64, (const unsigned char*)c->d_tile_slow, (unsigned int)wb,
-                               err, count, rows, part, peers, rp, 1.0, listed_late);
-          HIPCHK(c, hipGetLastError());
-        }
-      }
-      c->last_regs = regs;
-      if (scan5) {
-        ScanLaunch sl; std::memset(&sl, 0, sizeof sl);
-        sl.keys = keys; sl.sp = sp; sl.rp = rp; sl.st = c->d_state; sl.fl = fl; sl.long_min = lmin;
-        // (a streamed / sharded training fills the arrays shard by shard: kept whole there; rows in a caller's buffer -- rmi_hip_set_rows_output --
-        //  may be gone or overwritten when the arrays are asked for: lean_fill derives them from the rows, so no lean outputs then)
-        const bool lean5 = c->lean && !c->stream_mode && !c->defer_sync && c->d_rows_ext == nullptr;
-        sl.out.leaf_start = leaf_start; sl.out.rows = rows; sl.out.partials = part;
-        sl.out.params = lean5 ? nullptr : params; sl.out.leaf_err = lean5 ? nullptr : err; sl.out.leaf_count = lean5 ? nullptr : count;
-        c->last_lean = lean5;
-        sl.peers = peers;
-        sl.host_split = (c->have_shard && c->shard_split_idx != ~0ull) ? 1 : 0;
-        sl.mono = scan_mono ? 1 : 0;
-        sl.max_waves = c->scan_waves;
-        sl.n_cu = (unsigned int)c->n_cu;
-        // the general form's kernel gets as many waves as tiles were left to it by the last training of this (key set, leaf count) -- twice
-        // that and 64 more; a first training, or one in which the list outgrows them, launches what the device holds
-        sl.listed_hint = (c->scan_hint_epoch == c->keys_epoch && c->scan_hint_L == L_own) ? c->scan_hint_n : ~0u;
-        sl.long_leaves = (c->scan_skew_epoch == c->keys_epoch && c->scan_skew_L == L_own) ? 1 : 0;
-        {
-          const uint64_t need = rmi_scan_tiles(c->dtype, n_it);
-          if (c->tile_list_cap < need) {
-            if (c->d_tile_list) (void)hipFree(c->d_tile_list);
-            c->d_tile_list = nullptr; c->tile_list_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_tile_list, need * 4));
-            c->tile_list_cap = need;
-          }
-        }
-        sl.tile_list = c->d_tile_list; sl.tile_cnt = c->d_flist_cnt + 2 * SG_REGIONS + 2;   // (zeroed by k_init with the list counters)
-        if (!c->d_gaps) HIPCHK(c, hipMalloc(&c->d_gaps, (size_t)SCAN_GAP_CAP * sizeof(GapRec)));
-        sl.gaps = (GapRec*)c->d_gaps; sl.gap_cnt = c->d_flist_cnt + 2 * SG_REGIONS + 1;   // (zeroed by k_init with the list counters)
-        if (rmi_scan_launch(ROOT, c->dtype, sl, s) != 0) { set_err(c, "internal: k_spline_scan is not built for root %d / key type %d", ROOT, c->dtype); return RMI_ERR_HIP; }
-        (void)rmi_scan_gaps_launch(c->dtype, sl, s);
-        nrec = sl.waves;
-      } else if (verify || regs) {
-      } else if constexpr (LEAF == K_LINEAR) {                            // (linear_spline leaves reach this point only with scan5)
-        if (lanes_fused)
-          hipLaunchKernelGGL((k_leaf_lanes<K, true, K_LINEAR>), dim3((unsigned)wb), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, c->d_lntab, fl, lmin, maxerr, run,
-                             L, err, count, rows, part, rp, peers);
-        else
-          hipLaunchKernelGGL((k_leaf_lanes<K, false, K_LINEAR>), dim3((unsigned)wb), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, c->d_lntab, fl, lmin, maxerr, run,
-                             L, err, count, rows, part, rp, peers);
-      }
-      mark();
-      // --- the leaves handed over (containers too long for the lockstep walk): one wave each, fit + error pass; the
-      //     listed leaves' share of the finalize, the aggregates, the result record ---
-      SgParams sgp; std::memset(&sgp, 0, sizeof sgp);
-      sgp.flist = fl; sgp.segs = c->d_segs; sgp.mode = 0; sgp.guard_k = c->guard_k;
-      c->last_sg = sgp;
-      unsigned long long* const segs = c->d_segs;
-      DevState* const dst = c->d_state;
-      unsigned long long* const fticket = c->d_flist_cnt + 2 * SG_REGIONS;
-      DevState* const hcopy = c->h_state_dev + (c->stream_mode ? c->stream_slot : 0);
-      GiantLeaf* const dgiant = giants ? c->d_giant : (GiantLeaf*)nullptr;
-      const unsigned long long hmin = giants ? (unsigned long long)c->host_min : ~0ull;
-      const bool fused = lanes_fused;
-      // (the early giant list only where the host runs the tail itself, behind its synchronisation)
-      const bool early = optimistic && giants && !c->defer_sync && c->h_giant != nullptr;
-      unsigned long long* const hg = c->h_giant;
-      hipEvent_t const evg = c->ev_giant;
-      const uint64_t hgn = c->giant_cap < rmi_hip_ctx::GIANT_EARLY_MAX ? c->giant_cap : rmi_hip_ctx::GIANT_EARLY_MAX;
-      auto tail = [=](auto&& mk) {
-        if constexpr (ROOT == K_CUBIC && LEAF == K_LINEAR) {
-          if (verify) hipLaunchKernelGGL((k_verify_listed<K_CUBIC, K>), dim3(1024), dim3(256), 0, s, keys, sp, rp, leaf_start, dst, fl);
-        }
-        // (one wave per listed leaf wherever possible: on skewed keys thousands of leaves are listed and each is a sequential chain)
-        if (early) {
-          hipLaunchKernelGGL((k_giant_scan<K>), dim3(SG_REGIONS), dim3(64), 0, s, keys, sp, leaf_start, dst, fl, dgiant, hmin);
-          (void)hipMemcpyAsync(hg, &dst->giant_count, 8, hipMemcpyDeviceToHost, s);
-          (void)hipMemcpyAsync(hg + 1, dgiant, hgn * sizeof(GiantLeaf), hipMemcpyDeviceToHost, s);
-          (void)hipEventRecord(evg, s);
-        }
-        hipLaunchKernelGGL((k_list<K, LEAF>), dim3(128 * SG_REGIONS), dim3(64), 0, s, keys, sp, leaf_start, dst, params, fl, sgp, maxerr, run, dgiant, hmin, !early);
-        mk();
-        // (waves' aggregate records: [0, wb); their 64 slice sums, by k_list_tail: [wb, wb + 64); the records of k_finalize_listed behind)
-        hipLaunchKernelGGL((k_list_tail<K>), dim3(2048), dim3(64), 0, s, keys, sp, leaf_start, dst, params, fl, segs, maxerr, run,
-                           fused ? (const StatsPartial*)part : (const StatsPartial*)nullptr, (unsigned int)nrec, part + nrec);
-        mk();
-        if (fused)
-          hipLaunchKernelGGL((k_finalize_listed<K>), dim3(FL_BLOCKS), dim3(FL_THREADS), 0, s, keys, sp, L, leaf_start, dst, params, maxerr, run, err, count, rows,
-                             fl, part + nrec, (unsigned int)SG_REGIONS, part + nrec + SG_REGIONS, fticket, dst, hcopy, (const GiantLeaf*)nullptr, hmin);
-      };
-      if (optimistic) {
-        const unsigned int nsl = (unsigned int)((nrec + LF_SLICE - 1) / LF_SLICE);
-        hipLaunchKernelGGL(k_lane_reduce, dim3(nsl), dim3(LF_SLICE), 0, s, (const StatsPartial*)part, (unsigned int)nrec, part + nrec + SG_REGIONS + 2 * FL_BLOCKS + 1,
-                           c->d_tickets, fl, dst, hcopy);
-        mark(); mark();
-        c->tail_armed = true;
-        c->giant_early = early;
-        c->tail_fn = [tail]() -> int { tail([]() {}); return RMI_OK; };
-      } else tail(mark);
+      hipLaunchKernelGGL((k_leaf_samples<ROOT, K>), dim3((LS_SAMPLES + 256) / 256), dim3(256), 0, s, a.keys, a.sp, rp, smp, li);
+      hipLaunchKernelGGL((k_leaf_search<ROOT, K, LS_ILP>), dim3((unsigned)sb), dim3(LS_BLOCK), 0, s, a.keys, a.sp, rp, a.leaf_start, c->d_state, (const double*)smp);
     }
-  } else if (pl >= 1) HIPCHK(c, hipEventRecord(c->ev[0], s));
-  if (lanes) {
-  } else if (sigma) {
-    if constexpr (LEAF == K_LINEAR || LEAF == K_LINEAR_SPLINE) {
-      { const int lrc = ensure_lists(); if (lrc != RMI_OK) return lrc; }
-      if (c->bkeys_cap < L_own) {
-        if (c->d_bkeys) (void)hipFree(c->d_bkeys);
-        c->d_bkeys = nullptr; c->bkeys_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_bkeys, 2 * L_own * 8));
-        c->bkeys_cap = L_own;
-      }
-      SgParams sgp; sgp.guard_k = c->guard_k; sgp.mode = c->fit_mode;
-      sgp.flist.ids = c->d_flist; sgp.flist.cnt = c->d_flist_cnt; sgp.flist.cap = c->flist_cap;
-      sgp.dbg = 0;
-      {
-        auto launch2 = [&](auto ring_tag, auto batch_tag) -> int {
-          constexpr int RING = decltype(ring_tag)::value, BATCH = decltype(batch_tag)::value;
-          uint64_t chunk = (n_it + c->sigma_waves - 1) / c->sigma_waves;
-          chunk = ((chunk + BATCH - 1) / BATCH) * BATCH;
-          if (chunk < (uint64_t)BATCH * 4) chunk = (uint64_t)BATCH * 4;     // (>= the window of the chunk rule, RING / 2)
-          sgp.chunk = chunk;
-          const uint64_t sblocks = (n_it + chunk - 1) / chunk;
-          sgp.recs = nullptr; sgp.rec_cnt = nullptr; sgp.rpw = 0; sgp.segs = c->d_segs;
-          if (LEAF == K_LINEAR && c->fit_mode == 2) {
-            // a stretch of a long leaf is at least RING / 2 - BATCH keys, or the only one of its wave
-            const uint64_t rpw = chunk / (RING / 2 - BATCH) + 3;
-            const uint64_t need = sblocks * rpw * sizeof(SgRec) + sblocks * 4;
-            if (c->recs_bytes < need) {
-              if (c->d_recs) (void)hipFree(c->d_recs);
-              c->d_recs = nullptr; c->recs_bytes = 0;
-              HIPCHK(c, hipMalloc(&c->d_recs, need));
-              c->recs_bytes = need;
-            }
-            sgp.recs = (SgRec*)c->d_recs; sgp.rec_cnt = (unsigned int*)((char*)c->d_recs + sblocks * rpw * sizeof(SgRec)); sgp.rpw = (unsigned int)rpw;
-          }
-          c->last_sg = sgp;
-          if (c->fit_mode == 2)
-            hipLaunchKernelGGL((k_sigma2<ROOT, K, RING, BATCH, true>), dim3((unsigned)sblocks), dim3(64), 0, s, keys, sp, rp, sgp, leaf_start, params, maxerr, c->d_state,
-                               (K*)c->d_bkeys - sp.leaf_lo, (K*)c->d_bkeys + c->bkeys_cap - sp.leaf_lo);
-          else
-            hipLaunchKernelGGL((k_sigma2<ROOT, K, RING, BATCH, false>), dim3((unsigned)sblocks), dim3(64), 0, s, keys, sp, rp, sgp, leaf_start, params, maxerr, c->d_state,
-                               (K*)c->d_bkeys - sp.leaf_lo, (K*)c->d_bkeys + c->bkeys_cap - sp.leaf_lo);
-          return RMI_OK;
-        };
-        // (4-byte keys: the ring holds them raw, twice as many in the same LDS, and the batch is four loads as well)
-        int lrc;
-        if constexpr (sizeof(K) == 4) lrc = launch2(std::integral_constant<int, 4096>{}, std::integral_constant<int, 1024>{});
-        else lrc = launch2(std::integral_constant<int, 2048>{}, std::integral_constant<int, 512>{});
-        if (lrc != RMI_OK) return lrc;
-        mark();
-      }
-    }
-  } else if (n_it == 0) {
-    mark();                                              // a shard without keys: every leaf is empty
+  }
+  if (!r.init_folded) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, 12, s));   // (k_lane_reduce's arrival counter, k_leaf_regs' list counter and group counter)
+  if (!r.search) {
+    launch_bounds<ROOT, K>(s, a.keys, a.n_it, a.sp, rp, a.leaf_start, c->d_state);
+    launch_fill(s, a.a_leaf_start, L_own + 1, c->d_tilemin);
+  }
+  HIPCHK(c, a.mark.begin());
+  // --- exact fit of 64 leaves per wave in lockstep, and their error pass behind it ---
+  const SgList fl = flist_of(c);
+  if (r.giants) { if (const int grc = arm_giants(c, a)) return grc; }
+  const PeerRows peers = peer_rows(c, r);
+  auto lanes = [&](auto fused, auto vroot) {
+    hipLaunchKernelGGL((k_leaf_lanes<K, decltype(fused)::value, K_LINEAR, decltype(vroot)::value>), dim3((unsigned)wb), dim3(64), 0, s, a.keys, a.sp, a.leaf_start,
+                       c->d_state, a.params, c->d_lntab, fl, lanes_long_min(c), a.maxerr, a.run, a.L, a.err, a.count, a.rows, c->d_partials, rp, peers);
+  };
+  if (r.pipeline == 4) {
+    if (const int grc = launch_regs<K>(c, r, rp, a, fl, peers)) return grc;
+  } else if (r.verify) {                                               // (the verification rides on the fused error pass)
+    if constexpr (ROOT == K_CUBIC) lanes(std::true_type{}, std::integral_constant<int, K_CUBIC>{});
+  } else if (r.fused) lanes(std::true_type{}, std::integral_constant<int, -1>{});
+  else lanes(std::false_type{}, std::integral_constant<int, -1>{});
+  a.mark();
+  launch_tail<ROOT, K_LINEAR, K>(c, r, rp, a, fl, wb);
+  if (!r.fused) launch_err_range<ROOT, K_LINEAR, K>(c, rp, a);
+  a.mark();
+  if (!r.fused) launch_finalize<K_LINEAR, K>(c, a, nullptr, nullptr);
+  a.mark();
+  return RMI_OK;
+}
+
+// Pipeline 5, linear_spline leaves: k_spline_scan (rmi_scan.hip) finds the leaf starts, fits and checks every leaf in one pass; the list tail.
+template <int ROOT, typename K>
+static int launch_scan(rmi_hip_ctx* c, const rmi_route::Route& r, const RootP& rp, Launch<K>& a) {
+  if (const int lrc = ensure_lists(c, a.n_it, a.L_own)) return lrc;
+  HIPCHK(c, a.mark.begin());
+  const SgList fl = flist_of(c);
+  ScanLaunch sl; std::memset(&sl, 0, sizeof sl); sl.keys = a.keys; sl.sp = a.sp; sl.rp = rp; sl.st = c->d_state; sl.fl = fl; sl.long_min = lanes_long_min(c);
+  sl.out.leaf_start = a.leaf_start; sl.out.rows = a.rows; sl.out.partials = c->d_partials;
+  sl.out.params = r.lean ? nullptr : a.params; sl.out.leaf_err = r.lean ? nullptr : a.err; sl.out.leaf_count = r.lean ? nullptr : a.count;
+  sl.peers = peer_rows(c, r);
+  sl.host_split = (c->have_shard && c->shard_split_idx != ~0ull) ? 1 : 0; sl.mono = r.scan_mono ? 1 : 0;
+  sl.max_waves = c->knobs.scan_waves; sl.n_cu = (unsigned int)c->n_cu; sl.listed_hint = r.listed_hint; sl.long_leaves = r.long_leaves ? 1 : 0;
+  if (const int grc = grow(c, c->d_tile_list, c->tile_list_cap, rmi_scan_tiles(c->dtype, a.n_it), 4)) return grc;
+  if (!c->d_gaps) HIPCHK(c, hipMalloc(&c->d_gaps, (size_t)SCAN_GAP_CAP * sizeof(GapRec)));   // (the counters: zeroed by k_init with the lists')
+  sl.tile_list = c->d_tile_list; sl.tile_cnt = c->d_flist_cnt + 2 * SG_REGIONS + 2; sl.gaps = (GapRec*)c->d_gaps; sl.gap_cnt = c->d_flist_cnt + 2 * SG_REGIONS + 1;
+  if (rmi_scan_launch(ROOT, c->dtype, sl, a.s) != 0) { set_err(c, "internal: k_spline_scan is not built for root %d / key type %d", ROOT, c->dtype); return RMI_ERR_HIP; }
+  (void)rmi_scan_gaps_launch(c->dtype, sl, a.s);
+  a.mark();
+  launch_tail<ROOT, K_LINEAR_SPLINE, K>(c, r, rp, a, fl, sl.waves);
+  a.mark(); a.mark();
+  return RMI_OK;
+}
+
+// The one-pass modes (rmi_hip_set_fit_mode 1 / 2), linear leaves: k_sigma2 from sufficient statistics, the fill, then the leaves it handed
+// over -- fit (or merge) + error pass, one wave per leaf, long ones in stretches -- and k_finalize.
+template <int ROOT, typename K>
+static int launch_sigma(rmi_hip_ctx* c, const rmi_route::Route& r, const RootP& rp, Launch<K>& a) {
+  hipStream_t s = a.s;
+  const uint64_t n_it = a.n_it, L_own = a.L_own;
+  HIPCHK(c, a.mark.begin());
+  if (const int lrc = ensure_lists(c, n_it, L_own)) return lrc;
+  if (const int grc = grow(c, c->d_bkeys, c->bkeys_cap, L_own, 2 * 8)) return grc;
+  SgParams sgp; sgp.guard_k = c->guard_k; sgp.mode = c->fit_mode; sgp.flist = flist_of(c); sgp.dbg = 0;
+  // (4-byte keys: the ring holds them raw, twice as many in the same LDS, and the batch is four loads as well)
+  constexpr int RING = sizeof(K) == 4 ? 4096 : 2048, BATCH = sizeof(K) == 4 ? 1024 : 512;
+  uint64_t chunk = ((n_it + c->sigma_waves - 1) / c->sigma_waves + BATCH - 1) / BATCH * BATCH;
+  if (chunk < (uint64_t)BATCH * 4) chunk = (uint64_t)BATCH * 4;         // (>= the window of the chunk rule, RING / 2)
+  const uint64_t sblocks = (n_it + chunk - 1) / chunk;
+  sgp.chunk = chunk; sgp.recs = nullptr; sgp.rec_cnt = nullptr; sgp.rpw = 0; sgp.segs = c->d_segs;
+  if (c->fit_mode == 2) {
+    const uint64_t rpw = chunk / (RING / 2 - BATCH) + 3;                // a stretch of a long leaf is at least RING / 2 - BATCH keys, or its wave's only one
+    if (const int grc = grow(c, c->d_recs, c->recs_bytes, sblocks * rpw * sizeof(SgRec) + sblocks * 4, 1)) return grc;
+    sgp.recs = (SgRec*)c->d_recs; sgp.rec_cnt = (unsigned int*)((char*)c->d_recs + sblocks * rpw * sizeof(SgRec)); sgp.rpw = (unsigned int)rpw;
+  }
+  c->last_sg = sgp;
+  K* const bn = (K*)c->d_bkeys - a.sp.leaf_lo, * const bp = (K*)c->d_bkeys + c->bkeys_cap - a.sp.leaf_lo;   // (the leaves' end keys)
+  if (c->fit_mode == 2)
+    hipLaunchKernelGGL((k_sigma2<ROOT, K, RING, BATCH, true>), dim3((unsigned)sblocks), dim3(64), 0, s, a.keys, a.sp, rp, sgp, a.leaf_start, a.params, a.maxerr, c->d_state, bn, bp);
+  else
+    hipLaunchKernelGGL((k_sigma2<ROOT, K, RING, BATCH, false>), dim3((unsigned)sblocks), dim3(64), 0, s, a.keys, a.sp, rp, sgp, a.leaf_start, a.params, a.maxerr, c->d_state, bn, bp);
+  a.mark();
+  launch_fill(s, a.a_leaf_start, L_own + 1, c->d_tilemin);
+  a.mark();
+  const SgList fl = sgp.flist;
+  // (the guarded mode re-fits its long leaves exactly: a giant one is a chain for a host core, as on the exact path;
+  //  RMI_FIT_ONEPASS merges their partial sums instead -- tagged entries, never handed to the host)
+  if (r.giants) {
+    if (const int grc = arm_giants(c, a)) return grc;
+    HIPCHK(c, launch_giant_list(c, a, fl));
+    c->giant_early = true;
+  }
+  hipLaunchKernelGGL((k_list<K, K_LINEAR>), dim3(128 * SG_REGIONS), dim3(64), 0, s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, fl, c->last_sg, a.maxerr, a.run,
+                     r.giants ? c->d_giant : (GiantLeaf*)nullptr, r.giants ? (unsigned long long)c->knobs.host_min : ~0ull, !r.giants);
+  a.mark();
+  hipLaunchKernelGGL((k_list_tail<K>), dim3(8192), dim3(64), 0, s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, fl, c->d_segs, a.maxerr, a.run);
+  a.mark();
+  launch_finalize<K_LINEAR, K>(c, a, bn, bp);
+  // (behind the host fit of giant leaves, giant_epilogue: every leaf finalized once more -- ~25 us -- and the aggregates)
+  if (r.giants) c->refinalize_fn = [c, a, bn, bp]() { launch_finalize<K_LINEAR, K>(c, a, bn, bp); };
+  a.mark();
+  return RMI_OK;
+}
+
+// Pipeline 2, the streaming passes of round 2: cubic and robust_linear leaves, tiny and huge key sets, RMI_HIP_PIPELINE=2.
+template <int ROOT, int LEAF, typename K>
+static int launch_passes(rmi_hip_ctx* c, const RootP& rp, Launch<K>& a) {
+  hipStream_t s = a.s;
+  const uint64_t n_it = a.n_it, L_own = a.L_own;
+  const bool stream_fit = LEAF == K_LINEAR && !c->robust_leaf;          // (linear leaves: fitted in the scan's pass)
+  HIPCHK(c, a.mark.begin());
+  if (n_it == 0) {
+    a.mark();                                                           // a shard without keys: every leaf is empty
   } else if (!stream_fit) {
-    // --- bucketing scan ---
-    {
-      constexpr uint64_t V = 16 / sizeof(K);
-      const uint64_t blocks = ((n_it + V - 1) / V + 256 * BV_UNROLL - 1) / (256 * BV_UNROLL);
-      hipLaunchKernelGGL((k_bounds_vec<ROOT, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, rp, leaf_start, c->d_state);
-    }
-    mark();
+    launch_bounds<ROOT, K>(s, a.keys, n_it, a.sp, rp, a.leaf_start, c->d_state);   // --- bucketing scan ---
+    a.mark();
   } else {
     // --- pass A: bucketing scan + exact per-leaf fit in one streaming pass ---
-    uint64_t C = (n_it + c->fit_threads - 1) / c->fit_threads;
-    C = ((C + FS_ROW - 1) / FS_ROW) * FS_ROW;
-    if (C < (uint64_t)c->fit_min_chunk) C = c->fit_min_chunk;
-    const uint64_t chunks = (n_it + C - 1) / C;
-    const uint64_t waves = (chunks + 63) / 64;
-    const uint64_t fblocks = (waves + FA_WAVES - 1) / FA_WAVES;
-    hipLaunchKernelGGL((k_fit_stream<ROOT, K>), dim3((unsigned)fblocks), dim3(64 * FA_WAVES), 0, s, keys, sp, rp, C, leaf_start, params, c->d_state, c->d_long, long_min_a);
-    mark();
+    const uint64_t C = pass_chunk(c, n_it, c->knobs.fit_threads), fblocks = (((n_it + C - 1) / C + 63) / 64 + FA_WAVES - 1) / FA_WAVES;
+    hipLaunchKernelGGL((k_fit_stream<ROOT, K>), dim3((unsigned)fblocks), dim3(64 * FA_WAVES), 0, s, a.keys, a.sp, rp, C, a.leaf_start, a.params, c->d_state, c->d_long,
+                       pass_a_long_min(c));
+    a.mark();
   }
-  // --- fill empty leaves ---
-  if (!lanes) {
-    const uint64_t count_e = L_own + 1;
-    const uint64_t ntiles = (count_e + FILL_TILE - 1) / FILL_TILE;
-    hipLaunchKernelGGL(k_fill_tilemin, dim3((unsigned)ntiles), dim3(256), 0, s, a_leaf_start, count_e, c->d_tilemin);
-    hipLaunchKernelGGL(k_fill_scan_tiles, dim3(1), dim3(1024), 0, s, c->d_tilemin, ntiles);
-    hipLaunchKernelGGL(k_fill_apply, dim3((unsigned)ntiles), dim3(256), 0, s, a_leaf_start, count_e, c->d_tilemin);
-  }
-  if (!lanes) mark();
-  bool sigma_giants = false;
-  if (lanes) {
-  } else if (sigma) {
-    if constexpr (LEAF == K_LINEAR || LEAF == K_LINEAR_SPLINE) {
-      // --- the leaves the one-pass kernel handed over: fit (or merge) + error pass, one wave per leaf; long ones in stretches ---
-      SgList fl; fl.ids = c->d_flist; fl.cnt = c->d_flist_cnt; fl.cap = c->flist_cap;
-      // (the guarded mode re-fits its long leaves exactly: a giant one is a chain for a host core, as on the exact path;
-      //  RMI_FIT_ONEPASS merges their partial sums instead -- tagged entries, never handed to the host)
-      sigma_giants = LEAF == K_LINEAR && c->host_min > 0 && (c->host_min_set || n_it / (L_own ? L_own : 1) <= c->host_min / 4) && !c->stream_mode && !c->defer_sync;
-      if (sigma_giants) {
-        const int grc = arm_giants(); if (grc != RMI_OK) return grc;
-        // (their list first, through pinned memory: the host walks those chains while k_list fits the other listed leaves)
-        const uint64_t hgn = c->giant_cap < rmi_hip_ctx::GIANT_EARLY_MAX ? c->giant_cap : rmi_hip_ctx::GIANT_EARLY_MAX;
-        hipLaunchKernelGGL((k_giant_scan<K>), dim3(SG_REGIONS), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, fl, c->d_giant, (unsigned long long)c->host_min);
-        HIPCHK(c, hipMemcpyAsync(c->h_giant, &c->d_state->giant_count, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(c->h_giant + 1, c->d_giant, hgn * sizeof(GiantLeaf), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->ev_giant, s));
-        c->giant_early = true;
-      }
-      hipLaunchKernelGGL((k_list<K, LEAF>), dim3(128 * SG_REGIONS), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, fl, c->last_sg, maxerr, run,
-                         sigma_giants ? c->d_giant : (GiantLeaf*)nullptr, sigma_giants ? (unsigned long long)c->host_min : ~0ull, !sigma_giants);
-      mark();
-      hipLaunchKernelGGL((k_list_tail<K>), dim3(8192), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, fl, c->d_segs, maxerr, run);
-    }
-  } else if (n_it == 0) {
+  launch_fill(s, a.a_leaf_start, L_own + 1, c->d_tilemin);             // --- fill empty leaves ---
+  a.mark();
+  if (n_it == 0) {
   } else if (!stream_fit) {
     // --- per-leaf fit ---
     const uint64_t blocks = (L_own + 255) / 256;
@@ -1697,67 +1436,117 @@ static int launch_pipeline(rmi_hip_ctx* c, const RootP& rp, uint64_t L) {
     if constexpr (LEAF == K_CUBIC) {
       // The cube of every container's key range is the platform libm's pow on the host (that is
       // what the reference's coefficient is defined by); the kernels do everything else.
-      if (c->cube_cap < L_own) {
-        if (c->d_cube) (void)hipFree(c->d_cube);
-        c->d_cube = nullptr; c->cube_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_cube, L_own * 8));
-        c->cube_cap = L_own;
-      }
+      if (const int grc = grow(c, c->d_cube, c->cube_cap, L_own, 8)) return grc;
       c->h_cube.resize(L_own);
-      hipLaunchKernelGGL((k_cubic_span<K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, leaf_start, c->d_state, c->d_cube - sp.leaf_lo);
+      hipLaunchKernelGGL((k_cubic_span<K>), dim3((unsigned)blocks), dim3(256), 0, s, a.keys, a.sp, a.leaf_start, c->d_state, c->d_cube - a.sp.leaf_lo);
       HIPCHK(c, hipMemcpyAsync(c->h_cube.data(), c->d_cube, L_own * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(c, hipStreamSynchronize(s));
       host_cubes(c->h_cube.data(), L_own);
       HIPCHK(c, hipMemcpyAsync(c->d_cube, c->h_cube.data(), L_own * 8, hipMemcpyHostToDevice, s));
-      cube = c->d_cube - sp.leaf_lo;
+      cube = c->d_cube - a.sp.leaf_lo;
     }
-    hipLaunchKernelGGL((k_fit_leaf<LEAF, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, leaf_start, c->d_state, params, cube, c->robust_leaf);
+    hipLaunchKernelGGL((k_fit_leaf<LEAF, K>), dim3((unsigned)blocks), dim3(256), 0, s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, cube, c->robust_leaf);
     if constexpr (LEAF == K_CUBIC) {
-      if (n_it + 2 > (uint64_t)CUBIC_LONG) {                 // long containers are possible
+      if (n_it + 2 > (uint64_t)CUBIC_LONG) {                           // long containers are possible
         const uint64_t wb = L_own < 4096 ? L_own : 4096;
-        hipLaunchKernelGGL((k_fit_cubic_long<K>), dim3((unsigned)wb), dim3(64), 0, s, keys, sp, leaf_start, c->d_state, params, cube);
+        hipLaunchKernelGGL((k_fit_cubic_long<K>), dim3((unsigned)wb), dim3(64), 0, s, a.keys, a.sp, a.leaf_start, c->d_state, a.params, cube);
       }
     }
   } else {
     // --- leaves handed over by pass A (more than long_min points): one wave each ---
     const uint64_t blocks = c->long_cap < 2048 ? c->long_cap : 2048;   // ~2 waves per SIMD saturate its f64 issue
-    hipLaunchKernelGGL((k_fit_long<ROOT, K>), dim3((unsigned)blocks), dim3(64), 0, s, keys, sp, rp, leaf_start, c->d_state, params, c->d_long);
+    hipLaunchKernelGGL((k_fit_long<ROOT, K>), dim3((unsigned)blocks), dim3(64), 0, s, a.keys, a.sp, rp, a.leaf_start, c->d_state, a.params, c->d_long);
   }
-  if (!sigma && !lanes) mark();
-  // --- error pass ---
-  if (n_it == 0 || sigma || lanes_fused) {
-  } else {
-    uint64_t C = (n_it + c->err_threads - 1) / c->err_threads;
-    C = ((C + FS_ROW - 1) / FS_ROW) * FS_ROW;
-    if (C < (uint64_t)c->fit_min_chunk) C = c->fit_min_chunk;
-    const uint64_t chunks = (n_it + C - 1) / C;
-    const uint64_t waves = (chunks + 63) / 64;
-    hipLaunchKernelGGL((k_err_range<ROOT, LEAF, K>), dim3((unsigned)waves), dim3(64), 0, s, keys, sp, rp, C, leaf_start, params, maxerr, run);
-  }
-  mark();
-  // --- finalize + stats ---
-  if (!lanes_fused) {
-    const uint64_t blocks = (L_own + 255) / 256;
-    const K* bn = sigma ? (const K*)c->d_bkeys - sp.leaf_lo : nullptr;
-    const K* bp = sigma ? (const K*)c->d_bkeys + c->bkeys_cap - sp.leaf_lo : nullptr;
-    hipLaunchKernelGGL((k_finalize<LEAF, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, L, leaf_start, c->d_state,
-                       params, maxerr, run, err, count, rows, c->d_partials, bn, bp);
-    // (the last kernel also copies the device state into the pinned host copy: a separate 100-byte
-    // copy command would cost ~15 us of the call)
-    hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, s, c->d_partials, (int)blocks, c->d_state, c->h_state_dev + (c->stream_mode ? c->stream_slot : 0));
-    if (sigma_giants) {
-      // (behind the host fit of giant leaves, giant_epilogue: every leaf finalized once more -- ~25 us -- and the aggregates)
-      StatsPartial* const part = c->d_partials;
-      DevState* const dst = c->d_state;
-      DevState* const hcopy = c->h_state_dev;
-      c->refinalize_fn = [=]() {
-        hipLaunchKernelGGL((k_finalize<LEAF, K>), dim3((unsigned)blocks), dim3(256), 0, s, keys, sp, L, leaf_start, dst, params, maxerr, run, err, count, rows, part, bn, bp);
-        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, s, part, (int)blocks, dst, hcopy);
-      };
+  a.mark();
+  if (n_it != 0) launch_err_range<ROOT, LEAF, K>(c, rp, a);            // --- error pass ---
+  a.mark();
+  launch_finalize<LEAF, K>(c, a, nullptr, nullptr);
+  a.mark();
+  return RMI_OK;
+}
+
+template <int ROOT, int LEAF, typename K>
+static int launch_pipeline(rmi_hip_ctx* c, const RootP& rp, uint64_t L, int root_kind, int leaf_kind) {
+  constexpr int PPL = (LEAF == K_CUBIC) ? 4 : 2;
+  constexpr int ROWB = PPL * 8 + 8;
+  Launch<K> a;
+  a.s = c->stream; a.mark = Marks{c, c->stream, c->profile_level, 0}; a.L = L;
+  // ---- index space of this launch (global indices; see Span) ----
+  Span& sp = a.sp;
+  if (c->have_shard) sp = c->shard;
+  else { sp.it_lo = 0; sp.it_hi = c->n; sp.rd_lo = 0; sp.rd_hi = c->n; sp.n = c->n; sp.leaf_lo = 0; sp.leaf_hi = L; }
+  const uint64_t n_it = a.n_it = sp.it_hi - sp.it_lo, L_own = a.L_own = sp.leaf_hi - sp.leaf_lo;   // keys and leaves of this launch
+  // pointers pre-offset so that ptr[global index] is the right element
+  // (streamed training: buffers of the whole key set / all leaves, indexed globally)
+  const uint64_t kb = c->stream_mode ? sp.rd_lo : 0, lb = c->stream_mode ? sp.leaf_lo : 0;
+  a.keys = (const K*)c->d_keys + kb - sp.rd_lo;
+  a.a_leaf_start = c->d_leaf_start + lb;
+  a.leaf_start = a.a_leaf_start - sp.leaf_lo; a.params = c->d_params + lb * PPL - sp.leaf_lo * PPL;
+  a.maxerr = c->d_maxerr + lb - sp.leaf_lo; a.run = c->d_run + lb - sp.leaf_lo;
+  a.err = c->d_err + lb - sp.leaf_lo; a.count = c->d_count + lb - sp.leaf_lo;
+  unsigned char* rows_base = c->d_rows_ext ? (unsigned char*)c->d_rows_ext : c->d_rows; c->last_rows = rows_base;
+  a.rows = rows_base + lb * ROWB - sp.leaf_lo * ROWB;
+
+  // --- init ---
+  // long-leaf list: a long leaf has at least long_min points, so n/long_min entries always suffice
+  uint64_t need_long = n_it / pass_a_long_min(c) + 1024;
+  if (c->fit_mode != 0 && need_long < L_own + 1024) need_long = L_own + 1024;      // one-pass mode: every listed leaf goes through k_fit_long
+  if (const int grc = grow(c, c->d_long, c->long_cap, need_long, 8)) return grc;
+  DevState& init = a.init; std::memset(&init, 0, sizeof init);
+  init.long_cap = c->long_cap; init.flag_cap = (uint64_t)L_own + 64; init.seg_cap = n_it / SG_SEG + L_own + 16;
+  init.giant_cap = c->knobs.host_min > 0 ? n_it / c->knobs.host_min + 64 : 0;
+  init.split_idx = (c->have_shard && c->shard_split_idx != ~0ull) ? c->shard_split_idx : sp.n;
+  init.split_target = (c->have_shard && c->shard_split_idx != ~0ull) ? c->shard_split_target : 0;
+  init.last_target = ~0ull; c->giant_armed = false;
+  if (!c->d_flist_cnt) HIPCHK(c, hipMalloc(&c->d_flist_cnt, (2 * SG_REGIONS + 8) * 8));  // (the one-pass mode's list + merge counters: zeroed by k_init)
+
+  // --- the route ---
+  rmi_route::RouteIn in;
+  in.root_kind = root_kind; in.leaf_kind = leaf_kind; in.key_type = c->dtype; in.n = sp.n; in.n_it = n_it; in.L_own = L_own;
+  in.slope_ok = rp.p1 >= 0.0 && std::isfinite(rp.p0) && std::isfinite(rp.p1);
+  in.cubic_finite = std::isfinite(rp.p0) && std::isfinite(rp.p1) && std::isfinite(rp.p2) && std::isfinite(rp.p3);
+  // the root facts that need the first and last resident key: each reads them once per key set (`epoch`: its cache of them)
+  int erc = RMI_OK;
+  auto edges = [&](uint64_t& epoch) {
+    K k[2] = {};
+    if (epoch == c->keys_epoch) return true;
+    if (hipMemcpy(&k[0], c->d_keys, sizeof(K), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&k[1], (const K*)c->d_keys + (c->n - 1), sizeof(K), hipMemcpyDeviceToHost) != hipSuccess) {
+      set_err(c, "reading the first and last key failed"); erc = RMI_ERR_HIP; return false;
     }
+    c->edge_first = rmi_host::as_uint(k[0]); c->edge_last = rmi_host::as_uint(k[1]);
+    c->edge_first_f = rmi_host::as_float(k[0]); c->edge_last_f = rmi_host::as_float(k[1]); epoch = c->keys_epoch;
+    return true;
+  };
+  const unsigned pfx = rp.prefix & 63u;
+  in.common_prefix = [&]() { return edges(c->edge_epoch) && (pfx == 0u || ((c->edge_first ^ c->edge_last) >> (64u - pfx)) == 0ull); };
+  in.cubic_increasing = [&]() { return edges(c->edgef_epoch) && cubic_increasing_on(rp, c->edge_first_f, c->edge_last_f); };
+  in.fit_mode = c->fit_mode; in.stream_mode = c->stream_mode; in.defer_sync = c->defer_sync; in.rows_ext = c->d_rows_ext != nullptr; in.peer_fuse_n = c->peer_fuse_n;
+  in.n_cu = c->n_cu;
+  c->mem.lookup({c->keys_epoch, L_own, c->fit_mode}, &in);
+  const rmi_route::Route r = rmi_route::plan_route(c->knobs, in);
+  if (erc != RMI_OK) return erc;
+  c->last_route = r;
+
+  if ((!c->stream_mode || c->stream_slot == 0) && a.mark.pl >= 0) HIPCHK(c, hipEventRecord(c->ev[8], a.s));   // start of the device work of this call
+  if (!r.init_folded) {                                                 // (else the launch of k_leaf_samples carries the init)
+    const bool init_arrays = r.pipeline != 5;                           // (k_spline_scan writes every leaf start itself)
+    const uint64_t ib = init_arrays ? (L_own + 1 + 255) / 256 : 1;
+    hipLaunchKernelGGL(k_init, dim3((unsigned)(ib < 2048 ? ib : 2048)), dim3(256), 0, a.s, a.a_leaf_start, c->d_maxerr + lb, c->d_run + lb,
+                       L_own, (unsigned long long)sp.it_hi, c->d_state, init, c->d_flist_cnt, 2 * SG_REGIONS + 8, init_arrays,
+                       r.pipeline == 5 ? c->d_tickets : (unsigned int*)nullptr);
   }
-  mark();
-  if (pl >= 0) HIPCHK(c, hipEventRecord(c->ev[9], s));
+  c->tail_armed = false; c->tail_fn = nullptr; c->regs_listed_fn = nullptr; c->refinalize_fn = nullptr;
+  c->giant_early = false; c->giant_fitted = false; c->lean_derived = false;
+  int rc;
+  if constexpr (LEAF == K_LINEAR)
+    rc = r.sigma ? launch_sigma<ROOT, K>(c, r, rp, a) : r.lanes() ? launch_leaf_lanes<ROOT, K>(c, r, rp, a) : launch_passes<ROOT, LEAF, K>(c, rp, a);
+  else if constexpr (LEAF == K_LINEAR_SPLINE)
+    rc = r.lanes() ? launch_scan<ROOT, K>(c, r, rp, a) : launch_passes<ROOT, LEAF, K>(c, rp, a);
+  else
+    rc = launch_passes<ROOT, LEAF, K>(c, rp, a);
+  if (rc != RMI_OK) return rc;
+  if (a.mark.pl >= 0) HIPCHK(c, hipEventRecord(c->ev[9], a.s));
   HIPCHK(c, hipGetLastError());
   return RMI_OK;
 }
@@ -1829,7 +1618,7 @@ static int giant_epilogue(rmi_hip_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->lp.params + 2 * g[i].j, &c->giant_ab[2 * i], 16, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(&c->d_state->seg_count, 0, 8, s));
   HIPCHK(c, hipMemsetAsync(c->d_flist_cnt + 2 * SG_REGIONS, 0, 8, s));
-  SgList fl; fl.ids = c->d_flist; fl.cnt = c->d_flist_cnt; fl.cap = c->flist_cap;
+  const SgList fl = flist_of(c);
   hipLaunchKernelGGL(k_giant_segments, dim3(16), dim3(64), 0, s, c->d_giant, c->lp.leaf_start, c->d_state, c->d_segs, c->lp.maxerr, c->lp.run);
   hipLaunchKernelGGL((k_list_tail<K>), dim3(2048), dim3(64), 0, s, keys, c->lp.sp, c->lp.leaf_start, c->d_state, c->lp.params, fl, c->d_segs, c->lp.maxerr, c->lp.run);
   if (c->refinalize_fn) {                                           // one-pass modes: k_finalize over all leaves + the aggregates again
@@ -1870,11 +1659,11 @@ static int giant_early_fit(rmi_hip_ctx* c) {
 }
 
 template <int ROOT, typename K>
-static int dispatch_leaf(rmi_hip_ctx* c, const RootP& rp, int leaf_kind, uint64_t L) {
+static int dispatch_leaf(rmi_hip_ctx* c, const RootP& rp, int root_kind, int leaf_kind, uint64_t L) {
   switch (leaf_kind) {
-    case RMI_MODEL_LINEAR: case RMI_MODEL_ROBUST_LINEAR: return launch_pipeline<ROOT, K_LINEAR, K>(c, rp, L);
-    case RMI_MODEL_LINEAR_SPLINE: return launch_pipeline<ROOT, K_LINEAR_SPLINE, K>(c, rp, L);
-    case RMI_MODEL_CUBIC: return launch_pipeline<ROOT, K_CUBIC, K>(c, rp, L);
+    case RMI_MODEL_LINEAR: case RMI_MODEL_ROBUST_LINEAR: return launch_pipeline<ROOT, K_LINEAR, K>(c, rp, L, root_kind, leaf_kind);
+    case RMI_MODEL_LINEAR_SPLINE: return launch_pipeline<ROOT, K_LINEAR_SPLINE, K>(c, rp, L, root_kind, leaf_kind);
+    case RMI_MODEL_CUBIC: return launch_pipeline<ROOT, K_CUBIC, K>(c, rp, L, root_kind, leaf_kind);
     default: return RMI_ERR_UNSUPPORTED_MODEL;
   }
 }
@@ -1883,13 +1672,13 @@ template <typename K>
 static int dispatch_root(rmi_hip_ctx* c, int root_kind, const RootP& rp, int leaf_kind, uint64_t L) {
   switch (root_kind) {
     case RMI_MODEL_LINEAR: case RMI_MODEL_ROBUST_LINEAR: case RMI_MODEL_LINEAR_SPLINE:
-      return dispatch_leaf<K_LINEAR, K>(c, rp, leaf_kind, L);     // all three predict with fma(beta, x, alpha)
-    case RMI_MODEL_CUBIC: return dispatch_leaf<K_CUBIC, K>(c, rp, leaf_kind, L);
-    case RMI_MODEL_LOGLINEAR: return dispatch_leaf<K_LOGLINEAR, K>(c, rp, leaf_kind, L);
-    case RMI_MODEL_NORMAL: return dispatch_leaf<K_NORMAL, K>(c, rp, leaf_kind, L);
-    case RMI_MODEL_RADIX: case RMI_MODEL_BRADIX: return dispatch_leaf<K_RADIX, K>(c, rp, leaf_kind, L);
+      return dispatch_leaf<K_LINEAR, K>(c, rp, root_kind, leaf_kind, L);     // all three predict with fma(beta, x, alpha)
+    case RMI_MODEL_CUBIC: return dispatch_leaf<K_CUBIC, K>(c, rp, root_kind, leaf_kind, L);
+    case RMI_MODEL_LOGLINEAR: return dispatch_leaf<K_LOGLINEAR, K>(c, rp, root_kind, leaf_kind, L);
+    case RMI_MODEL_NORMAL: return dispatch_leaf<K_NORMAL, K>(c, rp, root_kind, leaf_kind, L);
+    case RMI_MODEL_RADIX: case RMI_MODEL_BRADIX: return dispatch_leaf<K_RADIX, K>(c, rp, root_kind, leaf_kind, L);
     case RMI_MODEL_RADIX8: case RMI_MODEL_RADIX18: case RMI_MODEL_RADIX22: case RMI_MODEL_RADIX26: case RMI_MODEL_RADIX28:
-      return dispatch_leaf<K_RADIX_TABLE, K>(c, rp, leaf_kind, L);
+      return dispatch_leaf<K_RADIX_TABLE, K>(c, rp, root_kind, leaf_kind, L);
     default: return RMI_ERR_UNSUPPORTED_MODEL;
   }
 }
@@ -2008,10 +1797,8 @@ static int finish_train(rmi_hip_ctx* c, int leaf_kind, uint64_t num_leaves, rmi_
   }
   c->last_L = L_own; c->last_ppl = ppl;
   c->lean_last_target = st.last_target;
-  if (c->last_scan && !c->stream_mode) {
-    c->scan_hint_epoch = c->keys_epoch; c->scan_hint_L = L_own; c->scan_hint_n = (unsigned int)(st.scan_listed < 0xFFFFFFFFull ? st.scan_listed : 0xFFFFFFFFull);
-    if (st.scan_listed > 512ull) { c->scan_skew_epoch = c->keys_epoch; c->scan_skew_L = L_own; }
-  }
+  const rmi_route::Route& r = c->last_route;
+  c->mem.learn({c->keys_epoch, L_own, c->fit_mode}, r, c->knobs, c->stream_mode, {st.scan_listed, st.flag_count, st.merged_count, st.regs_listed});
   c->lean_leaf_lo = c->have_shard ? c->shard.leaf_lo : 0;
   std::memset(out, 0, sizeof *out);
   out->generation = c->generation;
@@ -2026,20 +1813,13 @@ static int finish_train(rmi_hip_ctx* c, int leaf_kind, uint64_t num_leaves, rmi_
   out->model_avg_log2_error = st.sum_log2 / (double)n_glob;
   out->model_max_log2_error = std::log2((double)st.max_err);
   out->split_idx = st.split_idx; out->split_target = st.split_target;
-  out->long_leaves = c->last_lanes ? st.flag_count : st.long_count;
-  if (c->last_sigma && (st.flag_count - st.merged_count) * 4 > L_own) {   // most leaves went through the list kernels: see hint_epoch
-    if (c->hint_epoch != c->keys_epoch || c->hint_mode != c->fit_mode) { c->hint_epoch = c->keys_epoch; c->hint_mode = c->fit_mode; c->hint_n = 0; }
-    c->hint_L[c->hint_n % 8] = L_own; c->hint_n++;
-  }
-  if (c->last_regs && c->regs_backoff && st.regs_listed >= (L_own + 63) / 64) c->last_regs = false;   // every group listed (regs_dups): k_leaf_lanes_listed did the work -- pipeline 3
-  if (c->regs_backoff && c->regs && (uint64_t)st.regs_listed * 4 > (L_own + 63) / 64) {   // most groups went on the list: see regs_off
-    if (c->regs_off_epoch != c->keys_epoch) { c->regs_off_epoch = c->keys_epoch; c->regs_off_n = 0; }
-    c->regs_off_L[c->regs_off_n % 8] = L_own; c->regs_off_n++;
-  }
-  out->fit_mode_used = c->last_sigma ? (c->last_spline ? RMI_FIT_USED_ONEPASS_EXACT : c->fit_mode) : 0;
-  out->exact_leaves = c->last_sigma ? st.flag_count - st.merged_count : 0;
-  out->merged_leaves = c->last_sigma ? (int32_t)(st.merged_count < 0x7fffffffull ? st.merged_count : 0x7fffffffull) : 0;
-  out->guard_leaves = c->last_sigma ? st.guard_count : 0;
+  out->long_leaves = r.lanes() ? st.flag_count : st.long_count;
+  // every group k_leaf_regs took listed (regs_dups): k_leaf_lanes_listed did the work -- reported as pipeline 3
+  if (r.pipeline == 4 && c->knobs.regs_backoff && st.regs_listed >= (L_own + 63) / 64) c->last_route.pipeline = 3;
+  out->fit_mode_used = r.sigma ? c->fit_mode : 0;
+  out->exact_leaves = r.sigma ? st.flag_count - st.merged_count : 0;
+  out->merged_leaves = r.sigma ? (int32_t)(st.merged_count < 0x7fffffffull ? st.merged_count : 0x7fffffffull) : 0;
+  out->guard_leaves = r.sigma ? st.guard_count : 0;
   float ms = 0.f;
   if (c->profile_level >= 0) HIPCHK(c, hipEventElapsedTime(&ms, c->ev[8], c->ev[9]));
   out->device_ns = (uint64_t)((double)ms * 1e6);
@@ -2049,10 +1829,6 @@ static int finish_train(rmi_hip_ctx* c, int leaf_kind, uint64_t num_leaves, rmi_
   }
   return RMI_OK;
 }
-
-extern "C" {
-
-}  // extern "C"
 
 // alpha, beta, error of every leaf from its row, its count from the bucket table (+ the last key's second visit, Q7)
 static __global__ void __launch_bounds__(256) k_lean_arrays(const unsigned char* __restrict__ rows, const unsigned long long* __restrict__ leaf_start, uint64_t L_own,
@@ -2066,7 +1842,7 @@ static __global__ void __launch_bounds__(256) k_lean_arrays(const unsigned char*
   count[j] = leaf_start[j + 1] - leaf_start[j] + ((leaf_lo + j == last_target) ? 1ull : 0ull);
 }
 static int lean_fill(rmi_hip_ctx* c) {
-  if (!c->last_lean || c->lean_derived || !c->last_L) return RMI_OK;
+  if (!c->last_route.lean || c->lean_derived || !c->last_L) return RMI_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t leaf_lo = c->lean_leaf_lo;
   hipLaunchKernelGGL(k_lean_arrays, dim3((unsigned)((c->last_L + 255) / 256)), dim3(256), 0, c->stream, (const unsigned char*)c->last_rows, (const unsigned long long*)c->d_leaf_start,
