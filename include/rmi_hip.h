@@ -152,6 +152,30 @@ int rmi_hip_abi_version(void);
  * kernel_ns[0] = k_leaf_regs, [1] = the groups it listed for k_leaf_lanes + k_regs_finalize, [2] = k_lane_reduce), 3 = k_leaf_lanes,
  * 2 = the streaming passes (tiny key sets, 2^32 keys and more, cubic leaves, the one-pass modes).  (v5) */
 int rmi_hip_last_pipeline(rmi_hip_ctx* ctx);
+/* Which branches the context's last training took, for tests and diagnosis (additive; the ABI version stays 6).  Read-only: the
+ * values are copied from what the context keeps after a training -- the planned route and the state record the last kernel
+ * published -- as they stand when the call returns; no device work.  From the route: `pipeline` (what rmi_hip_last_pipeline
+ * reports: a pipeline-4 training whose every group was listed reads 3), `regs` (the k_leaf_regs variant that was launched:
+ * 0, 1 = LONG, 2 = 4-byte keys at two waves per SIMD, -1 = none), `search` (leaf boundaries by k_leaf_search), `verify`
+ * (cubic root: every key's target verified by k_leaf_lanes), `cubic_margin` (cubic root on pipeline 4: the per-leaf margin of
+ * k_regs_finalize), `sigma` (the one-pass kernel), `scan_mono` / `long_leaves` (k_spline_scan: the short form of a tile is
+ * allowed; the long-leaf instance), `giants` (leaves beyond RMI_HIP_HOST_MIN go to host cores).  From the record: `regs_listed`
+ * (groups of 64 leaves k_leaf_regs left to k_leaf_lanes_listed), `scan_listed` (tiles the short form of k_spline_scan left to
+ * the general form), `long_count` (long-leaf list of the streaming passes), `giant_count` (leaves fitted on the host),
+ * `flag_count` (leaves handed to the list kernels), `merged_count`, `seg_count` (stretches of the listed leaves' error pass),
+ * `regs_dups` (leaves of the sampled stretches whose boundary probes met two equal keys).  Only the counters of the
+ * kernels that the route launched are meaningful.  After a streamed training the record is that of its first chunk; the worker contexts of
+ * rmi_hip_train_many are not reachable: their routes stay unknown.  RMI_ERR_BAD_ARG before the first training and after a training that
+ * returned an error (like the downloads: there is no result to speak of).  Read it before anything else runs on the context: later
+ * work on the context (an index built from the result, its searches) does not train, but only a read right behind the training is
+ * certain to see that training's record. */
+typedef struct {
+  int32_t pipeline, regs;
+  int32_t search, verify, cubic_margin, sigma, scan_mono, long_leaves, giants;
+  int32_t _pad;
+  uint64_t regs_listed, scan_listed, long_count, giant_count, flag_count, merged_count, seg_count, regs_dups;
+} rmi_hip_route_info;
+int rmi_hip_last_route_info(rmi_hip_ctx* ctx, rmi_hip_route_info* out);
 int rmi_hip_device_count(void);
 int rmi_hip_create(int device_id, rmi_hip_ctx** out);
 void rmi_hip_destroy(rmi_hip_ctx* ctx);

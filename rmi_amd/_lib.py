@@ -42,6 +42,13 @@ class Result(C.Structure):
     ]
 
 
+class RouteInfo(C.Structure):
+    _fields_ = [("pipeline", C.c_int32), ("regs", C.c_int32), ("search", C.c_int32), ("verify", C.c_int32), ("cubic_margin", C.c_int32),
+                ("sigma", C.c_int32), ("scan_mono", C.c_int32), ("long_leaves", C.c_int32), ("giants", C.c_int32), ("_pad", C.c_int32),
+                ("regs_listed", C.c_uint64), ("scan_listed", C.c_uint64), ("long_count", C.c_uint64), ("giant_count", C.c_uint64),
+                ("flag_count", C.c_uint64), ("merged_count", C.c_uint64), ("seg_count", C.c_uint64), ("regs_dups", C.c_uint64)]
+
+
 class SearchStats(C.Structure):
     _fields_ = [("queries", C.c_uint64), ("fallbacks", C.c_uint64), ("root_oob", C.c_uint64), ("device_ns", C.c_uint64)]
 
@@ -50,6 +57,7 @@ class SearchStats(C.Structure):
 SYMBOLS = [
     ("rmi_hip_abi_version", C.c_int, []),
     ("rmi_hip_last_pipeline", C.c_int, [C.c_void_p]),
+    ("rmi_hip_last_route_info", C.c_int, [C.c_void_p, C.POINTER(RouteInfo)]),
     ("rmi_hip_device_count", C.c_int, []),
     ("rmi_hip_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     ("rmi_hip_destroy", None, [C.c_void_p]),

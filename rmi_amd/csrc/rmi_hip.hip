@@ -213,6 +213,18 @@ extern "C" {
 
 int rmi_hip_abi_version(void) { return RMI_HIP_ABI_VERSION; }
 int rmi_hip_last_pipeline(rmi_hip_ctx* c) { return !c ? RMI_ERR_BAD_ARG : c->last_route.pipeline; }
+int rmi_hip_last_route_info(rmi_hip_ctx* c, rmi_hip_route_info* out) {
+  if (!c || !out || !c->last_L || !c->h_state) return RMI_ERR_BAD_ARG;   // (last_L: the last training succeeded and its arrays stand)
+  const rmi_route::Route& r = c->last_route;
+  const DevState& st = *c->h_state;
+  std::memset(out, 0, sizeof *out);
+  out->pipeline = r.pipeline; out->regs = r.regs;
+  out->search = r.search; out->verify = r.verify; out->cubic_margin = r.cubic_margin; out->sigma = r.sigma;
+  out->scan_mono = r.scan_mono; out->long_leaves = r.long_leaves; out->giants = r.giants;
+  out->regs_listed = st.regs_listed; out->scan_listed = st.scan_listed; out->long_count = st.long_count; out->giant_count = st.giant_count;
+  out->flag_count = st.flag_count; out->merged_count = st.merged_count; out->seg_count = st.seg_count; out->regs_dups = st.regs_dups;
+  return RMI_OK;
+}
 
 int rmi_hip_device_count(void) {
   int n = 0;

@@ -123,6 +123,24 @@ class TrainedRMI:
     _trainer: object = field(default=None, repr=False)
     _cache: dict = field(default_factory=dict, repr=False)
 
+    @property
+    def route(self):
+        """Which branches this training took (rmi_hip_last_route_info) as a dict: the planned route and the counters of the kernels that
+        ran.  Read from the trainer's context on first use, like the per-leaf arrays, and with their rule: fetch it before the trainer
+        trains again or is closed (``materialize()`` does), or get a ``RuntimeError``.  Read it right behind the training where the
+        counters matter.  None for the results of ``train_many`` (their contexts are the library's own)."""
+        if "route" not in self._cache:
+            tr = self._trainer
+            if tr is None:
+                return None
+            if tr._h is None:
+                raise RuntimeError("the trainer of this result has been closed: read the route first (materialize())")
+            if tr._generation != self.generation:
+                raise RuntimeError("this trainer has trained again since: the route of the earlier result is gone "
+                                   "(call materialize() on a result before the next train call)")
+            self._cache["route"] = tr.last_route()
+        return self._cache["route"]
+
     def _get(self, what: str):
         """Per-leaf arrays live in the trainer's context until its next train call: fetch them before
         (``materialize()``), or get a ``RuntimeError`` instead of another training's arrays."""
@@ -132,7 +150,7 @@ class TrainedRMI:
 
     def materialize(self) -> "TrainedRMI":
         """Download every per-leaf array now (the object then no longer depends on the trainer)."""
-        _ = self.leaf_params, self.last_layer_max_l1s, self.leaf_counts, self.leaf_starts, self.rows
+        _ = self.leaf_params, self.last_layer_max_l1s, self.leaf_counts, self.leaf_starts, self.rows, self.route
         return self
 
     @property
@@ -176,6 +194,7 @@ class Trainer:
         self._keepalive = None
         self._table_in_ctx = None
         self._ctx_lock = threading.RLock()
+        self._generation = 0                      # rmi_hip_result.generation of the last training through this object
         self.n = 0
         if keys is not None:
             self.set_keys(keys)
@@ -350,6 +369,7 @@ class Trainer:
         return self._result(res, root, leaf_kind, num_leaves)
 
     def _result(self, res, root: Model, leaf_kind: int, num_leaves: int) -> TrainedRMI:
+        self._generation = int(res.generation)
         return TrainedRMI(
             num_rmi_rows=int(res.num_rows), num_data_rows=int(res.num_rows),
             model_avg_error=res.model_avg_error, model_avg_l2_error=res.model_avg_l2_error,
@@ -364,6 +384,17 @@ class Trainer:
                      "sum_n_err": int(res.sum_n_err), "sum_l2": float(res.sum_l2), "sum_log2": float(res.sum_log2)},
             fit_mode_used=int(res.fit_mode_used), exact_leaves=int(res.exact_leaves), merged_leaves=int(res.merged_leaves), guard_leaves=int(res.guard_leaves),
             generation=int(res.generation), pipeline=int(self._lib.rmi_hip_last_pipeline(self._h)), _trainer=self)
+
+    def last_route(self):
+        """Which branches the context's last training took (rmi_hip_last_route_info): the fields of the record as a dict, the
+        route's switches as bools; None before the first training, or with a library that lacks the call (RMI_HIP_LIB)."""
+        fn = getattr(self._lib, "rmi_hip_last_route_info", None)
+        info = _lib.RouteInfo()
+        with self._ctx_lock:
+            if fn is None or self._h is None or fn(self._h, C.byref(info)) != 0:
+                return None
+        flags = ("search", "verify", "cubic_margin", "sigma", "scan_mono", "long_leaves", "giants")
+        return {n: (bool(getattr(info, n)) if n in flags else int(getattr(info, n))) for n, _ in _lib.RouteInfo._fields_ if not n.startswith("_")}
 
     def train_many(self, configs, in_flight: int = 4):
         """rmi_hip_train_many: `configs` = [(root Model, leaf kind or name, branching factor), ...] on the resident keys, in ONE call
@@ -398,6 +429,7 @@ class Trainer:
         self.last_many_errors = {int(m.group(1)): m.group(2).strip() for m in
                                  re.finditer(r"configuration (\d+): (.*?)(?=; configuration \d+: |$)", self.last_many_error, re.S)}
         out = []
+        own_generation = self._generation                         # (the results carry the worker contexts' counters)
         for i, (root, _leaf, L) in enumerate(configs):
             if int(rcs[i]) != 0:
                 out.append((int(rcs[i]), None))
@@ -406,6 +438,7 @@ class Trainer:
             t._trainer = None
             t.pipeline = 0                                        # (rmi_hip_last_pipeline speaks of the caller's context only: not known per configuration)
             out.append((0, t))
+        self._generation = own_generation
         return out
 
     def release_views(self):

@@ -29,5 +29,11 @@ int main(void) {
   F(rmi_hip_result, sum_log2); F(rmi_hip_result, device_ns); F(rmi_hip_result, kernel_ns); F(rmi_hip_result, long_leaves);
   F(rmi_hip_result, fit_mode_used); F(rmi_hip_result, merged_leaves); F(rmi_hip_result, exact_leaves); F(rmi_hip_result, guard_leaves);
   F(rmi_hip_result, generation);
+  SZ(rmi_hip_route_info);
+  F(rmi_hip_route_info, pipeline); F(rmi_hip_route_info, regs); F(rmi_hip_route_info, search); F(rmi_hip_route_info, verify);
+  F(rmi_hip_route_info, cubic_margin); F(rmi_hip_route_info, sigma); F(rmi_hip_route_info, scan_mono); F(rmi_hip_route_info, long_leaves);
+  F(rmi_hip_route_info, giants); F(rmi_hip_route_info, regs_listed); F(rmi_hip_route_info, scan_listed); F(rmi_hip_route_info, long_count);
+  F(rmi_hip_route_info, giant_count); F(rmi_hip_route_info, flag_count); F(rmi_hip_route_info, merged_count); F(rmi_hip_route_info, seg_count);
+  F(rmi_hip_route_info, regs_dups);
   return 0;
 }

@@ -54,6 +54,7 @@ def _check(monkeypatch, oracle, env, keys, root, L, leaf="linear", mode=0, coef_
     assert abs(g.model_avg_log2_error - o.model_avg_log2_error) <= 1e-9 * max(1.0, abs(o.model_avg_log2_error))
     rows = g.rows.view(np.uint64).reshape(L, 3)
     assert np.array_equal(rows[:, :2], g.leaf_params.view(np.uint64)) and np.array_equal(rows[:, 2], g.last_layer_max_l1s)
+    g.materialize()                                          # (the route of the training too: callers assert on g.route)
     tr.close()
     return g
 

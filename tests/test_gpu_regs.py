@@ -51,6 +51,9 @@ def test_regs_variants(monkeypatch, oracle, variant, gen, n, L, root):
         # (every group listed -- by the switch, because the boundary search met duplicates, or because every group met keys whose f64 images
         #  collapse: k_leaf_lanes_listed did the work, reported as 3)
         assert g.pipeline in ((3, 4) if (gen.startswith("dups") or gen == "clustered_u64") else (4,))
+        if g.pipeline == 4:                                  # the variant the comment of VARIANTS promises (4-byte keys: two waves per SIMD by default)
+            want = 2 if gen.endswith("u32") else (1 if variant == "long" or (variant != "any_average" and n > 208 * L) else 0)
+            assert g.route["regs"] == want and g.route["search"]
 
 
 @pytest.mark.parametrize("u32", ["0", "1", "2"])
@@ -60,9 +63,10 @@ def test_regs_four_byte_keys_every_route(monkeypatch, oracle, u32, gen, n, L, ro
     default), 1 = the one-wave kernel in half-line panels (short and LONG variants by the average), 0 = k_leaf_lanes.  Same bits as the oracle every way."""
     g = _check(monkeypatch, oracle, {"RMI_HIP_REGS": "1" if u32 != "0" else "", "RMI_HIP_REGS_U32": u32}, dg.GENERATORS[gen](n), root, L)
     if g is not None and u32 == "0":
-        assert g.pipeline == 3
+        assert g.pipeline == 3 and g.route["regs"] == -1
     if g is not None and u32 != "0" and gen == "uniform_u32" and root != "cubic":
         assert g.pipeline == 4
+        assert g.route["regs"] == (2 if u32 == "2" else (1 if n > 208 * L else 0))
 
 
 @pytest.mark.parametrize("name", sorted(dg.ADVERSARIAL))
