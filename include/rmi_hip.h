@@ -459,6 +459,9 @@ void* rmi_hip_device_rows(rmi_hip_ctx* ctx);
  * Where the emitted C++ has no defined result the device defines one and counts the query in `root_oob`:
  *   - a root without a bounds check whose raw prediction lies outside [0, L): the leaf index is clamped to [0, L-1];
  *   - a NaN root prediction (f64 queries): leaf 0.  A NaN leaf prediction gives guess 0 (Rust's saturating `as u64`).
+ * search compares with `<`, as std::lower_bound over the emitted code's keys would: pos = the count of resident keys < q.  That is
+ * np.searchsorted(keys, q, "left") for every query but a NaN: no key is < NaN, so a NaN query answers 0 (numpy sorts NaN behind
+ * every key and answers n).  Its counters are the ones above: leaf 0, guess 0, one root_oob, no fallback.
  * A model without error rows (errors == NULL, the emitted `--no-errors` code) has err = 0 for every leaf: search gallops
  * from the guess, lookup writes no err.  Bounded RMIs (cache_fix) are not indexed (RMI_ERR_UNSUPPORTED_MODEL at the
  * caller that knows the model is bounded: the rows alone do not say so).

@@ -6,6 +6,10 @@
 * ``search(q)``  -> ``pos = lower_bound(keys, q)`` over the trainer's resident keys (``np.searchsorted(keys, q, "left")``);
 * ``verify()``   -> ``(checked, outside)``: the reference's acceptance loop over every resident key.
 
+``search`` compares with ``<``, as ``std::lower_bound`` over the emitted code's keys would: ``pos = (keys < q).sum()``.  That is
+``np.searchsorted`` for every query but a NaN: no key is ``< NaN``, so a NaN query answers 0 (numpy sorts NaN behind every key and
+answers n); it reads leaf 0, guesses 0, and counts as one ``root_oob`` and no fallback.
+
 Queries are a numpy array (staged to the device through the trainer's context) or a torch tensor on the trainer's device
 (used in place through ``data_ptr()``); the outputs come back in the same kind (torch outputs as int64 tensors on the device;
 torch brings a HIP runtime of its own, which must be the first one the process initialises).  The

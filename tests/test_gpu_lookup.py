@@ -94,9 +94,12 @@ def test_lookup_matches_emitted_cpp_and_search_is_exact(tmp_path, gen, root, lea
             assert ix.last_stats.fallbacks == 0
             assert np.array_equal(pos, np.searchsorted(keys, perm, side="left").astype(np.uint64))
     # the cooperative variant answers the same
-    ix.set_variant("coop")
     q = np.concatenate(list(ld.query_sets(keys, seed=3).values()))
+    ix.search(q, positions=False)
+    lane_fallbacks = ix.last_stats.fallbacks
+    ix.set_variant("coop")
     assert np.array_equal(ix.search(q), np.searchsorted(keys, q, side="left").astype(np.uint64))
+    assert ix.last_stats.fallbacks == lane_fallbacks
     ix.close()
     tr.close()
 
